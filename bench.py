@@ -41,20 +41,31 @@ clock starts after the opening barrier and stops once its device work has
 completed, before the closing barrier; the time is the max over ranks. Every
 one of the K steps runs in full inside the window.
 
-    python bench.py                       # N=1
-    torchrun --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8
+    python bench.py                       # N=1, the headline alone
+    python bench.py --full                # N=1, the headline and every extra below
+    torchrun --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8 --full
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+``--full`` adds what is measured in runs of their own: the phase breakdown
+(``window_phases``) and the extras below. ``--dump-outputs DIR`` writes the
+field the K timed steps left (what a caller of ``run(K)`` reads back) to
+``DIR/field.npy`` (``field_rank<r>.npy`` with peers), in the field's own dtype:
+the whole tile up to 4 Mi cells, else a fixed sample of 4 Mi cells (drawn from
+``seed + rank``, its first 16 Ki on the four edges). The inputs depend on the
+arguments alone, so two builds run with the same arguments compare cell by cell.
 
 Self-description (extras): the executed super-steps and exchanges (``halo``,
 ``timed_super_steps``, ``timed_exchanges``), the opening prepare() chose and
 the per-round maxima over ranks it decided on (``schedule_choice``), the RCCL
 communicator's own rank count and every rank's device (``rccl_ranks``,
-``rank_devices``), an event-timed phase breakdown of one untimed replica of the
-window (``window_phases``: pack / RCCL / unpack / passes / host overhead), and
-every MXS_* / NCCL_* / RCCL_* / HIP_* / HSA_* variable that was set (``env``).
+``rank_devices``), with ``--full`` an event-timed phase breakdown of one untimed
+replica of the window (``window_phases``: pack / RCCL / unpack / passes / host
+overhead), and every MXS_* / NCCL_* / RCCL_* / HIP_* / HSA_* variable that was
+set (``env``).
 An experiments build (-DMXS_EXPERIMENTS=ON, where MXS_* tuning knobs take effect)
 with such a knob set refuses to report a headline.
 
-Extras (not the headline number, BASELINE configs 2/3/5):
+Extras (``--full``; not the headline number, BASELINE configs 2/3/5):
   * every N: the parallel dot product, 2^30 fp64 split over the N ranks,
     single-pass device reduction + RCCL all-reduce of the partial (GB/s read);
   * N = 1: 8192^2 fp32 and fp64 single-GPU stencil rates;
@@ -78,6 +89,8 @@ import torch
 
 PINGPONG_SIZES = [8 << i for i in range(26)]  # 8 B .. 256 MiB
 SUMMARY_SIZES = {"1MiB": 1 << 20, "16MiB": 16 << 20, "256MiB": 256 << 20}
+DUMP_CELLS = 4 << 20  # --dump-outputs: cells written per rank (16 MiB as fp32, 32 MiB as fp64)
+DUMP_EDGE_CELLS = 4 << 10  # of a sample, on each of the four edges
 
 
 ENV_PREFIXES = ("MXS_", "NCCL_", "RCCL_", "HIP_", "HSA_", "GPU_", "ROCR_", "ROC_", "TORCH_NCCL_")
@@ -163,6 +176,30 @@ def stencil_rate(ctx, gw, gh, dtype, steps, warmup, warm_s=0.0, **kw) -> float:
     rate = st.cells_per_step * steps / dt / 1e9
     del st
     return rate
+
+
+def dump_outputs(st, ctx, out_dir: str) -> str:
+    """Write this rank's field as the timed steps left it to ``out_dir``; returns
+    the file. Up to DUMP_CELLS cells the whole tile, else DUMP_CELLS cells at
+    positions drawn from ``seed + rank`` (the first 4 x DUMP_EDGE_CELLS of them
+    moved onto the top, bottom, left and right edge, where the periodic wrap or
+    a neighbour's halo feeds the update)."""
+    import numpy as np
+
+    st.synchronize()
+    core = st.core_view()
+    h, w = core.shape
+    if h * w > DUMP_CELLS:
+        g = torch.Generator().manual_seed(st.cfg.seed + ctx.rank)
+        ys = torch.randint(0, h, (DUMP_CELLS,), generator=g)
+        xs = torch.randint(0, w, (DUMP_CELLS,), generator=g)
+        k = DUMP_EDGE_CELLS
+        ys[:k], ys[k:2 * k], xs[2 * k:3 * k], xs[3 * k:4 * k] = 0, h - 1, 0, w - 1
+        core = core[ys.to(core.device), xs.to(core.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, "field.npy" if ctx.world_size == 1 else f"field_rank{ctx.rank}.npy")
+    np.save(path, core.detach().cpu().contiguous().numpy())
+    return path
 
 
 def dot_extras(ctx, extras: dict, n_global: int) -> None:
@@ -410,7 +447,14 @@ def main(argv=None) -> int:
     p.add_argument("--direct-engine", default="kernel", choices=["kernel", "copy-engine"],
                    help="with --direct-halo validate: what pushes the bands, a CU kernel or the SDMA copy engines")
     p.add_argument("--no-graph", action="store_true")
-    p.add_argument("--no-extras", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline also measure what takes runs of its own: the window's phase breakdown "
+                        "and the extras (dot product, other stencil sizes / precisions / forms, ping-pong)")
+    p.add_argument("--no-extras", action="store_true",
+                   help="with --full: keep the phase breakdown, skip the extras (a plain run has neither)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write the field they left to DIR/field.npy (field_rank<r>.npy with "
+                        "peers): the whole tile, or a fixed seeded sample of a large one")
     p.add_argument("--clock-warmup-ms", type=float, default=200.0,
                    help="untimed, state-preserving passes of the timed kernel shapes before the window, so a "
                         "short window runs at sustained clocks (0 = off)")
@@ -552,12 +596,17 @@ def main(argv=None) -> int:
         props = torch.cuda.get_device_properties(dev)
         me = f"{dev}:{getattr(props, 'pci_bus_id', '?')}:{getattr(props, 'gcnArchName', props.name)}"
         extras["rank_devices"] = [b.decode() for b in ctx.allgather_bytes(me.encode(), key="mxs/bench/devices")]
-        # One untimed, state-preserving replica of the window's opening super-step,
-        # event-timed phase by phase (collective).
-        try:
-            extras["window_phases"] = st.profile_window(args.steps)
-        except Exception as e:  # noqa: BLE001 - diagnostic only
-            extras["window_phases_error"] = str(e)[:200]
+        if args.full:
+            # One untimed, state-preserving replica of the window's opening super-step,
+            # event-timed phase by phase (collective).
+            try:
+                extras["window_phases"] = st.profile_window(args.steps)
+            except Exception as e:  # noqa: BLE001 - diagnostic only
+                extras["window_phases_error"] = str(e)[:200]
+    if args.dump_outputs:
+        # After the record's own reads of the solver: reading the field tells the
+        # solver that it may have been written.
+        extras["outputs_file"] = dump_outputs(st, ctx, args.dump_outputs)
     # The tiles go back to torch's cache, not to the driver: freeing GPU memory
     # (hipFree, e.g. through torch.cuda.empty_cache) starts the driver's
     # background wipe of the freed VRAM, and HBM reads run ~4.5% slower while it
@@ -571,7 +620,7 @@ def main(argv=None) -> int:
         print(f"headline measured: {value:.3f} Gcells/s, {_ms(dt / args.steps)} ms/step, n_gpus={n}",
               file=sys.stderr, flush=True)
 
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         try:
             dot_extras(ctx, extras, args.dot_n)
         except Exception as e:  # noqa: BLE001

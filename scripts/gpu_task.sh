@@ -95,7 +95,7 @@ task_window() {
   if [ "${1:-}" = "--serial" ]; then modes="auto serial fused"; elif [ $# -gt 0 ]; then modes="$*"; fi
   for i in $(seq "$reps"); do
     for mode in $modes; do
-      local args=(--global "$tile" --steps "${WINDOW_STEPS:-20}" --warmup 5 --no-extras)
+      local args=(--global "$tile" --steps "${WINDOW_STEPS:-20}" --warmup 5 --full --no-extras)
       local base=$mode envs=()
       case $base in *-aw) envs+=(ROC_ACTIVE_WAIT_TIMEOUT=2000); base=${base%-aw} ;; esac
       if [[ $base =~ ^(.*)-cw([0-9]+)$ ]]; then args+=(--clock-warmup-ms "${BASH_REMATCH[2]}"); base=${BASH_REMATCH[1]}; fi
@@ -159,8 +159,8 @@ task_tune() {  # BIN FOCUS [ARGS]: the in-process tuners (build/bin/stencil_tune
 task_final() {
   task_tests || exit $?
   task_smoke
-  task_bench --steps 20 --warmup 5
-  task_prof driver --steps 20 --warmup 5
+  task_bench --steps 20 --warmup 5 --full
+  task_prof driver --steps 20 --warmup 5 --full
 }
 
 task_warmab() {  # REPS: the driver's N = 1 command with clock warm-up 200 ms (default) vs 1000 ms, interleaved
@@ -168,7 +168,7 @@ task_warmab() {  # REPS: the driver's N = 1 command with clock warm-up 200 ms (d
   : > "$OUT/warmab.jsonl"
   for i in $(seq "$reps"); do
     for w in 200 1000; do
-      timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-extras --clock-warmup-ms "$w" > "$OUT/warm_last.txt" 2>&1 || {
+      timeout -k 10 300 python bench.py --steps 20 --warmup 5 --full --no-extras --clock-warmup-ms "$w" >"$OUT/warm_last.txt" 2>&1 || {
         echo "bench failed"; tail -20 "$OUT/warm_last.txt"; exit 1; }
       python - "$OUT/warm_last.txt" "$w" >> "$OUT/warmab.jsonl" <<'PY'
 import json, sys
@@ -192,7 +192,7 @@ task_warmsweep() {  # REPS TILE W...: the driver's window (--steps 20) after W m
   : > "$OUT/warmsweep_$tile.jsonl"
   for i in $(seq "$reps"); do
     for w in "$@"; do
-      timeout -k 10 300 python bench.py --global "$tile" --steps 20 --warmup 5 --no-extras --clock-warmup-ms "$w" \
+      timeout -k 10 300 python bench.py --global "$tile" --steps 20 --warmup 5 --full --no-extras --clock-warmup-ms "$w" \
         > "$OUT/warm_last.txt" 2>&1 || { echo "bench failed"; tail -20 "$OUT/warm_last.txt"; exit 1; }
       python - "$OUT/warm_last.txt" "$w" >> "$OUT/warmsweep_$tile.jsonl" <<'PY'
 import json, sys

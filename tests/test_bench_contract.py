@@ -34,6 +34,55 @@ def test_bench_single_rank_cpu():
     assert ex["clock_warmup_ms"] == 200.0 and ex["untimed_warm_passes"] == 0
 
 
+def test_bench_plain_run_is_lean_and_dumps_the_timed_field(tmp_path):
+    """Without --full: the headline alone (no dot, no other sizes, no phase
+    breakdown). --dump-outputs writes the field the W + K steps left; the same
+    arguments give the same cells, and they are K + W Jacobi steps of the seeded
+    input (fp32: at most 5 roundings of 2^-24 relative per step on values in
+    [0, 1), 8 steps -> 2.4e-6)."""
+    import numpy as np
+    import torch
+
+    from cuda_mpi_scratch_amd.models.stencil2d import StencilConfig
+    from cuda_mpi_scratch_amd.ops import jacobi_reference_global, random_values
+
+    argv = ["--global", "128x96", "--steps", "6", "--warmup", "2", "--dump-outputs"]
+    got = []
+    for name in ("a", "b"):
+        r = run_ranks("bench", 1, {"argv": argv + [str(tmp_path / name)]})
+        d = _check(r[0]["line"], 1, 6, 2)
+        ex = d["extras"]
+        assert d["ms_per_step"] > 0 and "window_phases" not in ex and not any(k.startswith("dot_") for k in ex)
+        assert sorted(os.listdir(tmp_path / name)) == ["field.npy"]
+        got.append(np.load(tmp_path / name / "field.npy"))
+    assert got[0].dtype == np.float32 and got[0].shape == (96, 128)
+    assert np.array_equal(got[0], got[1])
+    ref = jacobi_reference_global(random_values(0, 0, 128, 96, 128, StencilConfig().seed), 8)
+    assert (torch.from_numpy(got[0]) - ref).abs().max().item() < 2.4e-6
+
+
+def test_bench_dump_samples_a_large_tile(tmp_path, monkeypatch):
+    """A tile above DUMP_CELLS is written as a fixed sample: DUMP_CELLS cells, the
+    same ones every time, the first 4 x DUMP_EDGE_CELLS on the four edges."""
+    import numpy as np
+
+    from cuda_mpi_scratch_amd.models.stencil2d import Stencil2D, StencilConfig
+    from cuda_mpi_scratch_amd.parallel.dist import DistContext
+
+    monkeypatch.setattr(bench, "DUMP_CELLS", 512)
+    monkeypatch.setattr(bench, "DUMP_EDGE_CELLS", 8)
+    ctx = DistContext()
+    st = Stencil2D(StencilConfig(global_width=64, global_height=48, dims="1x1", dtype="f64"), ctx, device="cpu")
+    st.run(2)
+    core = st.core_view().numpy()
+    a = np.load(bench.dump_outputs(st, ctx, str(tmp_path / "a")))
+    b = np.load(bench.dump_outputs(st, ctx, str(tmp_path / "b")))
+    assert a.dtype == np.float64 and a.shape == (512,) and np.array_equal(a, b)
+    for i, edge in enumerate((core[0], core[-1], core[:, 0], core[:, -1])):
+        assert np.isin(a[8 * i:8 * i + 8], edge).all()
+    assert np.isin(a, core).all() and len(np.unique(a)) > 256
+
+
 def test_bench_env_record_and_refusal(monkeypatch):
     """Every MXS_* / NCCL_* / ... variable that is set is recorded; an experiments
     build (where the MXS_* tuning knobs take effect) with one set refuses to
@@ -50,14 +99,15 @@ def test_bench_env_record_and_refusal(monkeypatch):
 
 
 def test_bench_single_rank_cpu_dot_extras():
-    r = run_ranks("bench", 1, {"argv": ["--global", "128x96", "--steps", "4", "--warmup", "1", "--dot-n", "4096"]})
+    r = run_ranks("bench", 1, {"argv": ["--global", "128x96", "--steps", "4", "--warmup", "1", "--full",
+                                        "--dot-n", "4096"]})
     ex = _check(r[0]["line"], 1, 4, 1)["extras"]
     assert ex["dot_4096_f64_verified"] is True and ex["dot_4096_f64_gbytes_per_s"] > 0
 
 
 def test_bench_two_ranks_cpu_extras():
     r = run_ranks("bench", 2, {"argv": ["--gpus", "2", "--global", "128x96", "--steps", "5", "--warmup", "1",
-                                        "--dot-n", "8192", "--pingpong-max", "4096"]})
+                                        "--full", "--dot-n", "8192", "--pingpong-max", "4096"]})
     assert r[1]["line"] is None and r[0]["rc"] == 0 and r[1]["rc"] == 0
     d = _check(r[0]["line"], 2, 5, 1)
     # MPI_Dims_create order: 2 ranks -> 2 rows x 1 col, printed rows first.
@@ -77,7 +127,7 @@ def test_bench_eight_ranks_cpu_walks_the_8gpu_path():
     """The N = 8 code path end to end (4 rows x 2 cols, torch halo backend on gloo):
     the same grid choice, exchange plan and extras the 8-GPU node runs."""
     r = run_ranks("bench", 8, {"argv": ["--gpus", "8", "--global", "256x128", "--steps", "3", "--warmup", "1",
-                                        "--dot-n", "65536", "--pingpong-max", "64"]}, timeout=240)
+                                        "--full", "--dot-n", "65536", "--pingpong-max", "64"]}, timeout=240)
     assert all(x["rc"] == 0 for x in r) and all(x["line"] is None for x in r[1:])
     d = _check(r[0]["line"], 8, 3, 1)
     assert d["config"]["parallelism"] == "cart4x2 (4 rows x 2 cols of ranks)"

@@ -22,7 +22,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_8gpu_tile_window_through_loopback(gpu):
     env = dict(os.environ, PYTHONUNBUFFERED="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--global", "16384x8192", "--loopback",
-                        "--rehearse-peers", "--steps", "20", "--warmup", "5", "--no-extras", "--clock-warmup-ms", "50"],
+                        "--rehearse-peers", "--steps", "20", "--warmup", "5", "--full", "--no-extras",
+                        "--clock-warmup-ms", "50"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -66,8 +67,8 @@ def test_bench_window_options_through_loopback(gpu, extra):
     after each RCCL transfer) run and say so in the record."""
     env = dict(os.environ, PYTHONUNBUFFERED="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--global", "16384x8192", "--loopback",
-                        "--rehearse-peers", "--steps", "20", "--warmup", "5", "--no-extras", "--clock-warmup-ms", "20",
-                        *extra], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
+                        "--rehearse-peers", "--steps", "20", "--warmup", "5", "--full", "--no-extras",
+                        "--clock-warmup-ms", "20", *extra], cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-2000:]
     ex = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["extras"]
     assert ex["timed_exchanges"] == 1
@@ -87,7 +88,7 @@ def test_bench_pingpong_and_dot_record_keys_through_loopback(gpu):
     next to its wall time."""
     env = dict(os.environ, PYTHONUNBUFFERED="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--global", "1024x1024", "--steps", "4",
-                        "--warmup", "1", "--pingpong-loopback", "--pingpong-max", str(1 << 20), "--dot-n",
+                        "--warmup", "1", "--full", "--pingpong-loopback", "--pingpong-max", str(1 << 20), "--dot-n",
                         str(1 << 22), "--clock-warmup-ms", "0"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]

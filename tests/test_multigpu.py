@@ -117,7 +117,7 @@ def test_bench_torchrun(gpu, n):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(root, "bench.py"),
-           "--gpus", str(n), "--steps", "20", "--warmup", "5", "--no-extras", "--comm-timeout", "120"]
+           "--gpus", str(n), "--steps", "20", "--warmup", "5", "--full", "--no-extras", "--comm-timeout", "120"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONUNBUFFERED="1")
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -153,7 +153,7 @@ def test_bench_pingpong_extras_two_gpus(gpu):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
            "127.0.0.1", "--master-port", str(free_port()), os.path.join(root, "bench.py"), "--gpus", "2",
            "--global", "4096x4096", "--steps", "20", "--warmup", "5", "--dot-n", str(1 << 24),
-           "--pingpong-max", str(1 << 24), "--comm-timeout", "120"]
+           "--pingpong-max", str(1 << 24), "--comm-timeout", "120", "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONUNBUFFERED="1")
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
