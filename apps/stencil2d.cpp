@@ -34,7 +34,8 @@
 // time-blocked kernels: bitwise equal to the CPU app; default: sum form when the coefficients are equal,
 // scaled form when they differ),
 // --loopback, --bind bunch|rrobin,
-// --dump / --no-dump, --checksum, --non-periodic, --seed S, --json FILE,
+// --dump / --no-dump, --checksum, --non-periodic, --block-fixed-edges (with --non-periodic: keep the time
+// block, the frame along the fixed edges on the held-side kernel), --seed S, --json FILE,
 // --checkpoint FILE / --resume FILE (collective MPI-IO global grid file, any
 // decomposition; same format as stencil2d_cpu and the Python package),
 // --comm-timeout SECONDS (halo watchdog, default 300), --fault-inject
@@ -93,8 +94,10 @@ int run(MpiEnv& env, const Cli& cli, const CartTopology& topo, const DeviceBindi
   // Temporal blocking (timed runs on the solver backends): S Jacobi steps per
   // launch on an S-deep ghost ring exchanged once per S steps.
   // A non-periodic grid has fixed boundary values that the S-step kernels
-  // would advance as cells: one exchange per iteration there (as the solver does).
-  const bool all_periodic = topo.periodic_rows && topo.periodic_cols;
+  // would advance as cells: one exchange per iteration there (as the solver
+  // does), unless --block-fixed-edges hands the frame to the held-side kernel.
+  const bool block_fixed = cli.flag("block-fixed-edges");
+  const bool all_periodic = (topo.periodic_rows && topo.periodic_cols) || block_fixed;
   const double c_center = cli.get_double("c-center", 0.2), c_neighbor = cli.get_double("c-neighbor", 0.2);
   // --no-sum-form: per-step evaluation everywhere (bitwise equal to the CPU app).
   const bool sum_form = !cli.flag("no-sum-form") && c_center == c_neighbor;
@@ -152,6 +155,7 @@ int run(MpiEnv& env, const Cli& cli, const CartTopology& topo, const DeviceBindi
   cfg.loopback_self = loopback;
   cfg.coeffs = {c_center, c_neighbor, sum_form};
   cfg.time_block = time_block;
+  cfg.block_fixed_edges = block_fixed;
   std::unique_ptr<StencilSolver<T>> solver;
   std::unique_ptr<MpiStagedHalo<T>> staged;
   const HaloPlan plan = make_halo_plan(topo, rank, g, true, loopback);
@@ -273,6 +277,7 @@ int run(MpiEnv& env, const Cli& cli, const CartTopology& topo, const DeviceBindi
         js << ", \"last_opening\": \"" << solver->last_run_opening() << "\"";
         if (!solver->steady_choice().empty()) js << ", \"steady_choice\": \"" << solver->steady_choice() << "\"";
         if (!solver->direct_state().empty()) js << ", \"direct_halo\": \"" << solver->direct_state() << "\"";
+        if (!solver->fixed_edge_note().empty()) js << ", \"fixed_edges\": \"" << solver->fixed_edge_note() << "\"";
       }
       if (want_sum) js << ", \"checksum\": " << app::fmt(checksum);
       js << app::meta_json(device_description(dev.device)) << "}";
@@ -294,7 +299,7 @@ int main(int argc, char** argv) {
   MpiEnv env(&argc, &argv);
   Cli cli(argc, argv, {"dump", "no-dump", "non-periodic", "strict-square", "no-overlap", "overlap", "no-graph",
                        "loopback", "pageable", "checksum", "halo-last", "no-sum-form",
-                       "no-direct-halo"});
+                       "no-direct-halo", "block-fixed-edges"});
   comm_timeout() = cli.get_double("comm-timeout", 300.0);
   const DeviceBinding dev = bind_device(env, cli.get("bind", "bunch"));
   const int n = env.size();

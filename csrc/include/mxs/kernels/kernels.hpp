@@ -19,6 +19,7 @@
 
 #include "mxs/grid/layout.hpp"
 #include "mxs/kernels/chunk_schedule.hpp"
+#include "mxs/kernels/fixed_edge_split.hpp"
 
 namespace mxs {
 namespace kernels {
@@ -176,6 +177,20 @@ constexpr bool stencil5_deep_supported(int steps, index_t x0, index_t x1) {
 template <typename T>
 void stencil5_tb(const T* in, T* out, const TileGeom& g, int steps, index_t x0, index_t x1, index_t y0, index_t y1,
                  Stencil5Coeffs c, bool wrap, hipStream_t s, StencilVariant v = StencilVariant::Auto);
+
+// The same contract as stencil5_tb(..., wrap = false) over [x0, x1) x [y0, y1),
+// except that at every one of the `steps` levels a cell outside the core on a
+// held side (`hold`: HoldSide bits, fixed_edge_split.hpp) keeps its input value:
+// the fixed boundary values of a physical edge. Ghost cells on the other sides
+// advance as cells (they are a neighbour's). An LDS tile that recomputes its
+// whole staged window at every level in the per-step form only: bitwise equal to
+// `steps` single steps, and with hold == 0 to the per-step stencil5_tb. Tile
+// shapes follow the rectangle (tall narrow for column strips, wide flat for row
+// strips, one general tile): it is meant for the frame of fixed_edge_split(),
+// not for the bulk. fp32 steps 1..kMaxTimeBlockDeep, fp64 1..kMaxTimeBlock.
+template <typename T>
+void stencil5_tb_held(const T* in, T* out, const TileGeom& g, int steps, index_t x0, index_t x1, index_t y0, index_t y1,
+                      Stencil5Coeffs c, unsigned hold, hipStream_t s);
 
 // ------------------------------------- chunk-list pass (interior-first super-step)
 // The S-step pass over chunks of the core of a ghost-ring tile (no wrap) on the

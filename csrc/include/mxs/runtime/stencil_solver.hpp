@@ -18,9 +18,20 @@
 //
 // Physical (non-periodic) edges: the S-step kernels advance the ghost ring as
 // ordinary cells at every intermediate level, which is exactly right for a
-// neighbour's cells but would overwrite fixed boundary values. A topology with
-// any non-periodic dimension therefore runs S = 1 (one exchange per iteration),
-// so every backend agrees with the S = 1 result.
+// neighbour's cells but would overwrite fixed boundary values. By default a
+// topology with any non-periodic dimension therefore runs S = 1 (one exchange
+// per iteration), so every backend agrees with the S = 1 result.
+// `block_fixed_edges` keeps the time block (Jacobi5): after S steps a fixed
+// edge has influenced only the cells within S of it, so each pass runs the
+// interior of kernels::fixed_edge_split() (the core shrunk by S on this rank's
+// held sides: the sides without a neighbour) on the same kernels as ever and
+// the frame, at most four strips S cells thick, on kernels::stencil5_tb_held,
+// which holds the outside cells at every level (per step: with the per-step
+// form the result is bitwise the S = 1 one; with the sum form the interior
+// differs by its usual few ulp). Boundary values live in the ghost ring of
+// BOTH buffers (no exchange writes a physical side). The schedules that pass
+// over the full core another way are off on every rank: the thin-strip
+// overlap and the interior-first opening (opening_reason() says so).
 //
 // Per super-step (cur -> nxt), serial (the default): the pass on the main
 // stream, then the exchange of its output (pack(nxt) -> RCCL -> unpack(nxt)):
@@ -148,6 +159,9 @@ struct SolverConfig {
   // up to kMaxTimeBlockDeep for fp32 without overlap: the two-stage pipeline;
   // larger requests are capped); the tile's ghost ring must be at least this deep.
   int time_block = 1;
+  // Keep `time_block` on a grid with fixed (non-periodic) edges (Jacobi5; see
+  // above). false: any non-periodic dimension runs S = 1.
+  bool block_fixed_edges = false;
   StencilKind kind = StencilKind::Jacobi5;
   kernels::Stencil5Coeffs coeffs;
   kernels::BoxWeights box;
@@ -364,6 +378,11 @@ class StencilSolver {
   // "fresh" (no priming exchange needed), "fused", "direct" or "" (no run).
   const std::string& last_run_opening() const { return last_opening_; }
   int time_block() const { return block_; }
+  // Fixed edges under time blocking: this rank's held sides and its split,
+  // e.g. "held sides: top,left; interior 4056x1980 + 2 frame strips at S = 20"
+  // ("" when inactive: periodic, block_fixed_edges off or S = 1).
+  std::string fixed_edge_note() const;
+  unsigned held_sides() const { return hold_; }
   // The halo communicator's CTA cap (0: RCCL's default) and why it is not the
   // requested one ("" when it is).
   int halo_max_ctas() const { return halo_comm_ ? halo_comm_->max_ctas() : 0; }
@@ -386,7 +405,13 @@ class StencilSolver {
   void enqueue_block(T* cur, T* nxt, int S);  // S <= block_ iterations, one exchange
   // `steps` iterations over core rows [r0, r1) x cols [c0, c1).
   void update(const T* in, T* out, int steps, index_t c0, index_t c1, index_t r0, index_t r1, hipStream_t s);
-  void core_pass(const T* cur, T* nxt, int S, hipStream_t s) { update(cur, nxt, S, 0, tile_.width, 0, tile_.height, s); }
+  void core_pass(const T* cur, T* nxt, int S, hipStream_t s);
+  // Fixed edges under time blocking (block_fixed_edges): the interior's column
+  // range in whole 4-cell vectors (the fp32 pipeline's and the fp64 wide
+  // pipeline's rule: stencil5_deep_supported, wide_pipe_ok).
+  static constexpr int kFixedEdgeVec = 4;
+  bool fixed_active_ = false;  // some rank holds a side at S > 1 (the same on every rank)
+  unsigned hold_ = 0;          // this rank's held sides (kernels::HoldSide)
   int last_forks_ = 0;
   // Graphs of `chain` consecutive super-steps of size S, one per buffer
   // orientation: g[0] starts from buf_a_, g[1] from buf_b_.

@@ -11,6 +11,7 @@
 #include "mxs/grid/regions.hpp"
 #include "mxs/halo/plan.hpp"
 #include "mxs/kernels/chunk_schedule.hpp"
+#include "mxs/kernels/fixed_edge_split.hpp"
 #include "mxs/runtime/decision.hpp"
 #include "mxs/topo/cart.hpp"
 
@@ -216,6 +217,26 @@ PYBIND11_MODULE(_mxs_core, m) {
       "opening) or its notch is below it (rule 'notch', the steady and direct-halo decisions) "
       "(runtime/decision.hpp); missing slots: kMissingSample");
   m.attr("MISSING_SAMPLE") = kMissingSample;
+  m.attr("HOLD_TOP") = unsigned(kernels::kHoldTop);
+  m.attr("HOLD_BOTTOM") = unsigned(kernels::kHoldBottom);
+  m.attr("HOLD_LEFT") = unsigned(kernels::kHoldLeft);
+  m.attr("HOLD_RIGHT") = unsigned(kernels::kHoldRight);
+  m.def(
+      "fixed_edge_split",
+      [](index_t w, index_t h, int S, int vec, unsigned hold) {
+        const kernels::FixedEdgeSplit sp = kernels::fixed_edge_split(w, h, S, vec, hold);
+        auto rect = [](const kernels::Rect& r) { return py::make_tuple(r.x0, r.x1, r.y0, r.y1); };
+        py::list frame;
+        for (int i = 0; i < sp.n_frame; ++i) frame.append(rect(sp.frame[i]));
+        py::dict d;
+        d["interior"] = rect(sp.interior);
+        d["frame"] = frame;
+        return d;
+      },
+      py::arg("width"), py::arg("height"), py::arg("steps"), py::arg("vec"), py::arg("hold"),
+      "time blocking beside fixed edges: the core's interior (x0, x1, y0, y1), shrunk by `steps` on the held sides "
+      "(HOLD_* bits; left / right to whole `vec`-cell vectors), and the frame rectangles that cover the rest "
+      "(kernels/fixed_edge_split.hpp); an empty interior is (0, 0, 0, 0)");
   m.def("balanced_starts", &kernels::balanced_starts, py::arg("groups"), py::arg("rows"), py::arg("blocks"),
         py::arg("fill"), "fill-aware linear starts of the pipeline workgroups' shares (blocks + 1 entries)");
   // Interior-first (halo-last) schedule of the multi-GPU opening super-step.

@@ -264,6 +264,27 @@ PYBIND11_MODULE(_mxs_hip, m) {
   m.def("last_pipe_lag1", &kernels::last_pipe_lag1,
         "whether the most recent stencil launch was a pipeline pass in ascending level order");
   m.def(
+      "stencil5_tb_held",
+      [](std::uintptr_t in, std::uintptr_t out, const TileGeom& g, int steps, index_t x0, index_t x1, index_t y0,
+         index_t y1, double c0, double c1, unsigned hold, const std::string& dt, std::uintptr_t s) {
+        kernels::Stencil5Coeffs c{c0, c1, false, -1.0};
+        if (parse_dtype(dt) == DType::F32)
+          kernels::stencil5_tb_held<float>(ptr<float>(in), ptr<float>(out), g, steps, x0, x1, y0, y1, c, hold, strm(s));
+        else
+          kernels::stencil5_tb_held<double>(ptr<double>(in), ptr<double>(out), g, steps, x0, x1, y0, y1, c, hold,
+                                            strm(s));
+      },
+      py::arg("src"), py::arg("dst"), py::arg("geom"), py::arg("steps"), py::arg("x0"), py::arg("x1"), py::arg("y0"),
+      py::arg("y1"), py::arg("c_center") = 0.2, py::arg("c_neighbor") = 0.2, py::arg("hold") = 15u,
+      py::arg("dtype") = "f32", py::arg("stream") = 0,
+      "S Jacobi steps over [x0, x1) x [y0, y1) of a ghost-ring tile beside fixed edges: cells outside the core on a "
+      "held side (hold: HOLD_TOP | HOLD_BOTTOM | HOLD_LEFT | HOLD_RIGHT) keep their input value at every level; "
+      "per-step form, bitwise equal to S single steps");
+  m.attr("HOLD_TOP") = unsigned(kernels::kHoldTop);
+  m.attr("HOLD_BOTTOM") = unsigned(kernels::kHoldBottom);
+  m.attr("HOLD_LEFT") = unsigned(kernels::kHoldLeft);
+  m.attr("HOLD_RIGHT") = unsigned(kernels::kHoldRight);
+  m.def(
       "stencil5_tb",
       [](std::uintptr_t in, std::uintptr_t out, const TileGeom& g, int steps, index_t x0, index_t x1, index_t y0,
          index_t y1, double c0, double c1, bool wrap, const std::string& dt, std::uintptr_t s,
@@ -450,8 +471,10 @@ PYBIND11_MODULE(_mxs_hip, m) {
                        py::object bootstrap, int graph_supersteps, bool sum_form, const std::string& direct_halo,
                        double graph_max_superstep_us, const std::string& opening, bool rehearse_peers,
                        double min_gain, int halo_max_ctas, int main_priority, int side_priority,
-                       double wire_delay_us, const std::string& direct_engine, const std::string& steady) {
+                       double wire_delay_us, const std::string& direct_engine, const std::string& steady,
+                       bool block_fixed_edges) {
              SolverConfig cfg;
+             cfg.block_fixed_edges = block_fixed_edges;
              if (steady == "auto") cfg.steady = Opening::Auto;
              else if (steady == "serial") cfg.steady = Opening::Serial;
              else if (steady == "interior-first") cfg.steady = Opening::InteriorFirst;
@@ -505,7 +528,7 @@ PYBIND11_MODULE(_mxs_hip, m) {
            py::arg("graph_max_superstep_us") = 150.0, py::arg("opening") = "auto", py::arg("rehearse_peers") = false,
            py::arg("min_gain") = 0.0, py::arg("halo_max_ctas") = 0, py::arg("main_priority") = -1,
            py::arg("side_priority") = 0, py::arg("wire_delay_us") = 0.0, py::arg("direct_engine") = "kernel",
-           py::arg("steady") = "auto",
+           py::arg("steady") = "auto", py::arg("block_fixed_edges") = false,
            py::keep_alive<1, 7>())
       .def("field_changed", [](SolverHandle& h) { h.visit([](auto& s) { s.field_changed(); }); },
            "the caller wrote the field: re-exchange the ghost ring and re-check the sum form's range next run")
@@ -534,6 +557,10 @@ PYBIND11_MODULE(_mxs_hip, m) {
             h.visit([op](auto& s) { s.force_steady(op); });
           },
           py::arg("steady"), "paired measurements: the later super-steps' schedule of the following calls")
+      .def("fixed_edge_note", [](SolverHandle& h) { return h.visit([](auto& s) { return s.fixed_edge_note(); }); },
+           "fixed edges under time blocking: this rank's held sides and its interior / frame split ('' when inactive)")
+      .def("held_sides", [](SolverHandle& h) { return h.visit([](auto& s) { return s.held_sides(); }); },
+           "this rank's held sides (HOLD_TOP | HOLD_BOTTOM | HOLD_LEFT | HOLD_RIGHT bits; 0 when inactive)")
       .def("multi_rank", [](SolverHandle& h) { return h.visit([](auto& s) { return s.multi_rank(); }); },
            "whether the solver follows the peers' schedule (remote peers or a loopback rehearsal)")
       .def("schedule_times",

@@ -40,8 +40,16 @@ StencilSolver<T>::StencilSolver(const CartTopology& topo, int rank, const TileGe
   // unpack / boundary launches should not queue behind the long interior sweep.
   block_ = cfg_.kind == StencilKind::Jacobi5 ? std::max(1, cfg_.time_block) : 1;
   // Fixed boundary values on a physical edge must not be advanced as cells:
-  // time blocking is only exact when every edge is a neighbour's (see header).
-  if (!(topo.periodic_rows && topo.periodic_cols)) block_ = 1;
+  // time blocking is only exact when every edge is a neighbour's, or
+  // (block_fixed_edges) with the frame along the physical sides on the
+  // held-side kernel (see header). Topology and configuration are the same on
+  // every rank, so every rank takes the same branch here.
+  const bool fixed_topo = !(topo.periodic_rows && topo.periodic_cols);
+  const bool block_fixed = fixed_topo && cfg_.block_fixed_edges && cfg_.kind == StencilKind::Jacobi5;
+  if (fixed_topo && !block_fixed) block_ = 1;
+  // The thin-strip overlap runs update() over the full width, held cells
+  // included: off (before the cap below, which keeps deep blocks for it).
+  if (block_fixed && block_ > 1) cfg_.overlap = false;
   // Blocks past kMaxTimeBlock run on the fp32 two-stage pipeline, which takes
   // whole-vector column ranges only: not the overlap schedule's thin strips,
   // not fp64, not a ragged width. Elsewhere the block is capped at 16.
@@ -62,6 +70,15 @@ StencilSolver<T>::StencilSolver(const CartTopology& topo, int rank, const TileGe
   MXS_CHECK(block_ <= tile_.width && block_ <= tile_.height,
             "time_block " << block_ << " exceeds the tile (" << tile_.width << "x" << tile_.height
                           << "): its ghost ring would reach past the neighbouring tiles");
+  // This rank's held sides: where the topology has no neighbour. An interior
+  // rank of a non-periodic grid holds none and runs the plain pass.
+  fixed_active_ = block_fixed && block_ > 1;
+  if (fixed_active_) {
+    if (topo.neighbor(rank, D_TOP) == kProcNull) hold_ |= kernels::kHoldTop;
+    if (topo.neighbor(rank, D_BOTTOM) == kProcNull) hold_ |= kernels::kHoldBottom;
+    if (topo.neighbor(rank, D_LEFT) == kProcNull) hold_ |= kernels::kHoldLeft;
+    if (topo.neighbor(rank, D_RIGHT) == kProcNull) hold_ |= kernels::kHoldRight;
+  }
   radius_ = cfg_.kind == StencilKind::Box ? cfg_.box.radius : 1;
   const int depth = std::max(radius_, block_);  // cells a super-step reads beyond the core
   MXS_CHECK(tile_.halo_x >= depth && tile_.halo_y >= depth,
@@ -128,7 +145,8 @@ StencilSolver<T>::StencilSolver(const CartTopology& topo, int rank, const TileGe
   const bool wire = cfg_.backend == HaloBackend::Rccl || cfg_.backend == HaloBackend::Ipc;
   halo_last_allowed_ = cfg_.opening != Opening::Serial && wire && !plan.sends.empty() &&
                        !fused_ && cfg_.kind == StencilKind::Jacobi5 &&
-                       cfg_.variant == kernels::StencilVariant::Auto && block_ > 1 && !cfg_.overlap;
+                       cfg_.variant == kernels::StencilVariant::Auto && block_ > 1 && !cfg_.overlap &&
+                       !fixed_active_;  // the chunk lists cover the full core, held cells included
   if (world_ > 1) {  // one rank without it (thin-strip overlap on a small tile) rules it out everywhere
     std::vector<double> v{halo_last_allowed_ ? 0.0 : 1.0};
     agree_max(v, "construction: opening agreement");
@@ -162,6 +180,10 @@ StencilSolver<T>::StencilSolver(const CartTopology& topo, int rank, const TileGe
   } else if (cfg_.opening == Opening::Serial) {
     opening_choice_ = "serial";
     opening_reason_ = "forced (opening = serial)";
+  }
+  if (fixed_active_) {  // some rank holds a side: every rank runs the serial schedule
+    opening_choice_ = "serial";
+    opening_reason_ = "serial: fixed edges (the interior-first opening and the thin-strip overlap pass over held cells)";
   }
   // Fast-form guard, coefficient part (the range part runs before the first
   // pass): the sum form (c_center == c_neighbor) or the scaled form (unequal,
@@ -218,6 +240,38 @@ void StencilSolver<T>::update(const T* in, T* out, int steps, index_t c0, index_
   }
 }
 
+// The whole core, cur -> nxt. With held sides and S > 1: the interior (S away
+// from every held side, so it reads no held cell at any level) on the usual
+// kernels, then the frame strips on the held-side kernel, on the same stream
+// (disjoint outputs, the same input).
+template <typename T>
+void StencilSolver<T>::core_pass(const T* cur, T* nxt, int S, hipStream_t s) {
+  const index_t w = tile_.width, h = tile_.height;
+  if (hold_ == 0 || S <= 1) return update(cur, nxt, S, 0, w, 0, h, s);
+  const kernels::FixedEdgeSplit sp = kernels::fixed_edge_split(w, h, S, kFixedEdgeVec, hold_);
+  update(cur, nxt, S, sp.interior.x0, sp.interior.x1, sp.interior.y0, sp.interior.y1, s);
+  for (int i = 0; i < sp.n_frame; ++i) {
+    const kernels::Rect& f = sp.frame[i];
+    kernels::stencil5_tb_held<T>(cur, nxt, tile_, S, f.x0, f.x1, f.y0, f.y1, cfg_.coeffs, hold_, s);
+  }
+}
+
+template <typename T>
+std::string StencilSolver<T>::fixed_edge_note() const {
+  if (!fixed_active_) return "";
+  if (hold_ == 0) return "held sides: none on this rank (other ranks hold the physical edges)";
+  std::string sides;
+  const char* names[4] = {"top", "bottom", "left", "right"};
+  for (int b = 0; b < 4; ++b)
+    if (hold_ & (1u << b)) sides += (sides.empty() ? "" : ",") + std::string(names[b]);
+  const kernels::FixedEdgeSplit sp = kernels::fixed_edge_split(tile_.width, tile_.height, block_, kFixedEdgeVec, hold_);
+  const kernels::Rect& in = sp.interior;
+  const std::string interior =
+      in.empty() ? "no interior" : "interior " + std::to_string(in.x1 - in.x0) + "x" + std::to_string(in.y1 - in.y0);
+  return "held sides: " + sides + "; " + interior + " + " + std::to_string(sp.n_frame) + " frame strip" +
+         (sp.n_frame == 1 ? "" : "s") + " at S = " + std::to_string(block_);
+}
+
 // Stream roles: the MAIN stream (the capture origin, high priority) carries the
 // exchange chain pack -> RCCL -> unpack and the boundary update; the interior
 // sweep forks onto the SIDE stream. RCCL calls must sit on the capture-origin
@@ -234,7 +288,7 @@ void StencilSolver<T>::enqueue_block(T* cur, T* nxt, int S) {
   }
   if (direct_on_) {  // the neighbours pushed cur's ghost ring after their previous pass
     direct_->wait(m);
-    update(cur, nxt, S, 0, w, 0, h, m);
+    core_pass(cur, nxt, S, m);
     direct_->push(nxt, m);
     return;
   }

@@ -67,6 +67,14 @@ class StencilConfig:
     # the sum form, else 12;
     # docs/PERF.md). Up to 32 for fp32 without overlap, else capped at 16.
     time_block: int = 0
+    # periodic=False on GPU: keep the time block (computed as for a periodic
+    # grid, the automatic default included) instead of one exchange per
+    # iteration. Each pass then runs the tile's interior, S cells away from the
+    # fixed edges, on the usual kernels and the frame along them on the
+    # held-side kernel (ops.stencil5_tb_held), which keeps the boundary values
+    # in the ghost ring fixed at every level. With sum_form=False the result is
+    # bitwise the one-exchange-per-iteration one.
+    block_fixed_edges: bool = False
     seed: int = 1234
     init: str = "random"             # random | rank
     graph_supersteps: int = 0        # super-steps per hipGraph launch (0 = auto, ~1 ms of work)
@@ -167,10 +175,11 @@ class Stencil2D:
             tb = int(self.ctx.allreduce_min(tb))
         # A physical (non-periodic) edge holds fixed boundary values that the
         # S-step kernels would advance as cells: time blocking needs every edge
-        # to be a neighbour's (the native solver enforces the same rule).
+        # to be a neighbour's, or block_fixed_edges (the frame along the fixed
+        # edges on the held-side kernel); the native solver enforces the same rule.
         self.time_block = (max(1, min(tb, d.width, d.height))
                            if (dev.type == "cuda" and cfg.kind == "jacobi5" and cfg.init != "rank"
-                               and cfg.periodic) else 1)
+                               and (cfg.periodic or cfg.block_fixed_edges)) else 1)
         h = max(h, self.time_block)
         C = core()
         if dev.type == "cuda":
@@ -236,7 +245,8 @@ class Stencil2D:
                                           self._direct_mode(backend),
                                           cfg.graph_max_superstep_us, cfg.opening, cfg.rehearse_peers, cfg.min_gain,
                                           cfg.halo_max_ctas, cfg.main_priority, cfg.side_priority,
-                                          cfg.wire_delay_us, cfg.direct_engine, cfg.steady)
+                                          cfg.wire_delay_us, cfg.direct_engine, cfg.steady,
+                                          block_fixed_edges=bool(cfg.block_fixed_edges and not cfg.periodic))
             # The solver may cap the request (blocks > 16 need the fp32 pipeline's
             # preconditions); the ghost ring was sized for the request.
             self.time_block = self.solver.time_block()
@@ -267,6 +277,60 @@ class Stencil2D:
             ops.fill(self.a, 0.0)
             ops.fill(self.b, 0.0)
             ops.fill_random(self.a, g, d.x0, d.y0, d.global_width, self.cfg.seed)
+
+    def set_boundary(self, top=None, bottom=None, left=None, right=None):
+        """Fixed boundary values of a non-periodic grid: each argument is a scalar
+        or a 1-D tensor over the GLOBAL width (top, bottom) or height (left,
+        right); None leaves that side as it is. Collective in spirit (every rank
+        calls it with the same values), no communication.
+
+        Every rank writes its slice into the ghost row / column adjacent to its
+        core on its physical sides, in both buffers (no exchange ever writes a
+        physical side, and a pass reads the ring of whichever buffer is
+        current). The slice includes the part beside a neighbour's ghost columns
+        / rows, clipped to the global range: a rank with a physical top and a
+        left neighbour holds row -1 over its left ghost columns too, and nobody
+        exchanges those cells (that diagonal has no rank), so boundary values
+        must come from this call or from the uniform initial ring. The four
+        outside corners are never read by a 5-point stencil. Ends with
+        field_changed()."""
+        d, g = self.decomp, self.geom
+        if self.cfg.periodic:
+            raise ValueError("set_boundary: the grid is periodic (StencilConfig.periodic=False has fixed edges)")
+        null = core().PROC_NULL
+        hx, hy = g.halo_x, g.halo_y
+        # Global index range of the ring row / column next to this tile, clipped.
+        gx_lo, gx_hi = max(0, d.x0 - hx), min(d.global_width, d.x0 + d.width + hx)
+        gy_lo, gy_hi = max(0, d.y0 - hy), min(d.global_height, d.y0 + d.height + hy)
+
+        def values(v, n, lo, hi, what):
+            if isinstance(v, torch.Tensor):
+                if v.dim() != 1 or v.numel() != n:
+                    raise ValueError(f"set_boundary: {what} must be a scalar or a 1-D tensor of {n} values")
+                return v[lo:hi].to(device=self.device, dtype=self.dtype)
+            return torch.full((hi - lo,), float(v), device=self.device, dtype=self.dtype)
+
+        self.synchronize()
+        for buf in (self.a, self.b):
+            full = buf.view(g.total_height(), g.pitch)[:, g.x_origin:g.x_origin + g.total_width()]
+            cols = slice(hx + gx_lo - d.x0, hx + gx_hi - d.x0)
+            rows = slice(hy + gy_lo - d.y0, hy + gy_hi - d.y0)
+            if top is not None and d.topo.shift(d.rank, 0, -1) == null:
+                full[hy - 1, cols] = values(top, d.global_width, gx_lo, gx_hi, "top")
+            if bottom is not None and d.topo.shift(d.rank, 0, 1) == null:
+                full[hy + g.height, cols] = values(bottom, d.global_width, gx_lo, gx_hi, "bottom")
+            if left is not None and d.topo.shift(d.rank, -1, 0) == null:
+                full[rows, hx - 1] = values(left, d.global_height, gy_lo, gy_hi, "left")
+            if right is not None and d.topo.shift(d.rank, 1, 0) == null:
+                full[rows, hx + g.width] = values(right, d.global_height, gy_lo, gy_hi, "right")
+        if self.device.type == "cuda":
+            torch.cuda.synchronize()
+        self.field_changed()
+
+    def fixed_edge_note(self) -> str:
+        """Time blocking beside fixed edges: this rank's held sides and its
+        interior / frame split ('' when inactive)."""
+        return self.solver.fixed_edge_note() if self.solver is not None else ""
 
     # ------------------------------------------------------------- stepping
     def step(self):
@@ -450,6 +514,8 @@ class Stencil2D:
             how = ("HIP IPC direct push of each pass's edge bands into the neighbours' tiles"
                    + (" by the SDMA copy engines" if self.cfg.direct_engine == "copy-engine" else ""))
         text = f"{what}; {ex} halo exchange{'s' if ex != 1 else ''} by {how}"
+        if self.solver.fixed_edge_note():
+            text += f"; fixed edges: {self.solver.fixed_edge_note()}"
         wd = self.solver.wire_delay_us()
         if wd:
             text += f" (+ {wd:g} us of rehearsed wire time after each transfer)"
@@ -550,6 +616,10 @@ def main(argv=None) -> int:
     p.add_argument("--c-neighbor", type=float, default=StencilConfig.c_neighbor)
     p.add_argument("--no-sum-form", action="store_true",
                    help="per-step evaluation (bitwise equal to S single steps) instead of the sum / scaled form")
+    p.add_argument("--non-periodic", action="store_true", help="fixed (non-periodic) edges on all four sides")
+    p.add_argument("--block-fixed-edges", action="store_true",
+                   help="with --non-periodic: keep the time block (interior on the usual kernels, the frame along "
+                        "the fixed edges on the held-side kernel) instead of one exchange per iteration")
     p.add_argument("--seed", type=int, default=StencilConfig.seed)
     p.add_argument("--checkpoint", default=None, help="write the final field to this grid file")
     p.add_argument("--resume", default=None, help="start from this grid file (any decomposition)")
@@ -566,7 +636,8 @@ def main(argv=None) -> int:
                         backend=args.backend, overlap=False if args.no_overlap else None, graph=not args.no_graph,
                         loopback=args.loopback, variant=args.variant, time_block=args.time_block,
                         seed=args.seed, opening=args.opening, steady=args.steady, c_center=args.c_center,
-                        c_neighbor=args.c_neighbor, sum_form=not args.no_sum_form)
+                        c_neighbor=args.c_neighbor, sum_form=not args.no_sum_form, periodic=not args.non_periodic,
+                        block_fixed_edges=args.block_fixed_edges)
     st = Stencil2D(cfg, ctx)
     if args.resume:
         hdr = st.load_checkpoint(args.resume)
@@ -584,7 +655,8 @@ def main(argv=None) -> int:
     gcells = st.cells_per_step * args.iters / dt / 1e9
     rec = {"metric": "stencil2d_gcells_per_s", "value": gcells, "ms_per_iter": dt / args.iters * 1e3,
            "ranks": ctx.world_size, "dims": f"{rows}x{cols}", "config": asdict(cfg), "backend": st.backend,
-           "graph": st.graph_status(), "iteration": st.iteration,
+           "graph": st.graph_status(), "iteration": st.iteration, "time_block": st.time_block,
+           "fixed_edges": st.fixed_edge_note(), "halo_mode": st.halo_mode(),
            "evaluation": ("scaled form" if st.scaled_form_active else "sum form" if st.sum_form_active
                           else "per step")}
     if args.checkpoint:

@@ -121,6 +121,58 @@ def jacobi_reference_global(u: torch.Tensor, iters: int, c_center=0.2, c_neighbo
     return u
 
 
+HOLD_TOP, HOLD_BOTTOM, HOLD_LEFT, HOLD_RIGHT = 1, 2, 4, 8  # kernels::HoldSide
+
+
+def stencil5_tb_held(src, dst, geom, steps, x0, x1, y0, y1, c_center=0.2, c_neighbor=0.2, hold=15, stream=None) -> None:
+    """``steps`` Jacobi iterations over core rectangle [x0, x1) x [y0, y1) of a
+    ghost-ring tile beside fixed edges, in one launch (GPU tensors only): cells
+    outside the core on a held side (``hold``: HOLD_* bits) keep their input
+    value at every level, ghost cells on the other sides advance as cells.
+    Per-step form: bitwise equal to ``steps`` single steps."""
+    if not src.is_cuda:
+        raise TypeError("stencil5_tb_held runs the HIP kernel: GPU tensors only (CPU: jacobi_held_reference)")
+    hip().stencil5_tb_held(src.data_ptr(), dst.data_ptr(), geom, steps, x0, x1, y0, y1, c_center, c_neighbor,
+                           int(hold), dtype_name(src), _stream(stream))
+
+
+def jacobi_held_reference(full: torch.Tensor, steps: int, c_center=0.2, c_neighbor=0.2, hold: int = 15,
+                          ring: int | None = None) -> torch.Tensor:
+    """Reference of the time-blocked pass beside fixed edges on a full (core +
+    ghost ring) 2-D array whose ring is ``ring`` cells deep (default: ``steps``).
+    Every step updates all cells but the outermost ring of the array, then
+    restores the cells outside the core on the held sides (``hold``: HOLD_*
+    bits) to their input values. The stale outermost ring reaches one cell
+    further in per step, so after ``steps <= ring`` steps the core is exact; the
+    arithmetic is jacobi_reference_global's (fp32 through fp64)."""
+    ring = steps if ring is None else ring
+    if steps > ring:
+        raise ValueError(f"jacobi_held_reference: {steps} steps need a ring of at least {steps} cells, got {ring}")
+    u0 = full.clone()
+    u = full.clone()
+    H, W = u.shape
+    for _ in range(steps):
+        c = u[1:-1, 1:-1]
+        sums = (u[:-2, 1:-1] + u[2:, 1:-1]) + (u[1:-1, :-2] + u[1:-1, 2:])
+        if u.dtype == torch.float32:
+            c1 = torch.tensor(c_neighbor, dtype=torch.float32).double()
+            prod = (torch.tensor(c_center, dtype=torch.float32) * c).double()
+            new = (c1 * sums.double() + prod).float()
+        else:
+            new = c_neighbor * sums + c_center * c
+        u = u.clone()
+        u[1:-1, 1:-1] = new
+        if hold & HOLD_TOP:
+            u[:ring, :] = u0[:ring, :]
+        if hold & HOLD_BOTTOM:
+            u[H - ring:, :] = u0[H - ring:, :]
+        if hold & HOLD_LEFT:
+            u[:, :ring] = u0[:, :ring]
+        if hold & HOLD_RIGHT:
+            u[:, W - ring:] = u0[:, W - ring:]
+    return u
+
+
 def jacobi_sum_reference_global(u: torch.Tensor, steps: int, c: float = 0.2) -> torch.Tensor:
     """One sum-form pass of `steps` levels on the periodic torus, in the exact
     association of the GPU sum bodies (stencil_device.hpp sum_rot4f / sum_w4d):
