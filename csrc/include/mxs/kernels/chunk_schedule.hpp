@@ -90,14 +90,19 @@ std::int64_t min_budget(const std::vector<Run>& runs, int blocks, std::int64_t f
 }  // namespace detail
 
 // Linear start index (group * rows + row) of each workgroup's range, blocks + 1
-// entries (the last = groups * rows); a workgroup with nothing to do has an
-// empty range.
+// entries (the last = the length of the space); a workgroup with nothing to do
+// has an empty range. last_rows > 0: the last group's run is only last_rows
+// (<= rows) long — a narrow last column group that the pass runs as two
+// half-height sub-groups side by side (stencil_device.hpp: the split group) —
+// so the space is (groups - 1) * rows + last_rows long; 0 = rows.
 inline std::vector<std::int64_t> balanced_starts(std::int64_t groups, std::int64_t rows, int blocks,
-                                                 std::int64_t fill) {
+                                                 std::int64_t fill, std::int64_t last_rows = 0) {
+  if (last_rows <= 0 || last_rows > rows) last_rows = rows;
   std::vector<detail::Run> runs;
-  for (std::int64_t g = 0; g < groups; ++g) runs.push_back(detail::Run{std::int32_t(g), 0, rows});
+  for (std::int64_t g = 0; g < groups; ++g)
+    runs.push_back(detail::Run{std::int32_t(g), 0, g + 1 == groups ? last_rows : rows});
   const std::int64_t T = detail::min_budget(runs, blocks, fill, [](int, std::int64_t t) { return t; });
-  std::vector<std::int64_t> start(size_t(blocks) + 1, groups * rows);
+  std::vector<std::int64_t> start(size_t(blocks) + 1, (groups - 1) * rows + last_rows);
   std::vector<std::uint8_t> seen(size_t(blocks), 0);
   detail::greedy_walk(runs, blocks, fill, [&](int) { return T; },
                       [&](int w, std::int32_t g, std::int64_t r0, std::int64_t) {

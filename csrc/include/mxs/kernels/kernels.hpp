@@ -150,12 +150,18 @@ inline int auto_time_block(index_t w, index_t h, int elem_bytes = 4, bool sum_fo
   if (elem_bytes == 4 && (w + 256) * 4 * kMinChunkRows > kMaxChunkBytes) return kMaxTimeBlock;
   if (elem_bytes == 4 && w >= 1024 && h >= 1024) {
     // The pipeline runs workgroups of 4 strips; with joint stage-1 windows a
-    // group stores 912 columns at S = 20 (12 + 8) and 904 at S = 24 (12 + 12),
-    // and a partial last group costs a whole one. S = 24 when it needs no more
-    // groups than S = 20 (4096 wide: 5 and 5); otherwise the extra group costs
-    // more than the deeper block saves (8192^2 sum form: 9 vs 10 groups,
-    // 8.6-8.9 T cells/s at S = 20 vs 8.4 at 24; 16384 wide: 18 vs 19 groups,
-    // 9.8-10.0 vs 9.4; profiles/r02_joint).
+    // group stores 912 columns at S = 20 (12 + 8) and 904 at S = 24 (12 + 12).
+    // A partial last group costs a whole one, except at S = 24 (ascending
+    // order) when at most 440 columns are left for it: then it is split and
+    // costs half (set_pipe_split). S = 24 when it needs no more groups than
+    // S = 20 (4096 wide: 5 and 5); otherwise the extra group cost more than
+    // the deeper block saved when this rule was measured, with whole last
+    // groups (8192^2 sum form: 9 vs 10 groups, 8.6-8.9 T cells/s at S = 20 vs
+    // 8.4 at 24; 16384 wide: 18 vs 19 groups, 9.8-10.0 vs 9.4;
+    // profiles/r02_joint). With the split (9.5 and 18.5 groups) S = 24 measures
+    // 1.3% (8192^2) and 3.8% (16384 x 8192) ahead of S = 20 in paired 240-step
+    // windows (profiles/pipe_split); the rule is kept as it is pinned by the
+    // policy test, the 8192^2 rate floor and the config-2 cycle budget.
     auto groups = [&](int owg) { return (w + owg - 1) / owg; };
     if (sum_form && groups(904) <= groups(912)) return 24;
     // Tiles of >= 2^30 cells (chunks of ~4800 rows, warm-up negligible): the
@@ -273,6 +279,18 @@ void set_pipe_lag1(bool on);
 bool pipe_lag1();
 // Whether the most recent stencil launch was a pipeline pass in that order.
 bool last_pipe_lag1();
+// The split narrow last column group of the fp32 S = 24 (12 + 12, ascending)
+// pipeline pass (stencil_device.hpp: pipe_split_form; default on): when at most
+// 440 columns are left for the last joint group, its workgroups run it as two
+// two-strip sub-groups on half the rows each, so it costs half a group per row
+// (32768 wide: 36.5 group-rows per row instead of 37). Off runs it as a whole
+// four-strip group. Bitwise equal output. MXS_PIPE_SPLIT=0 in the environment
+// turns it off at start-up.
+void set_pipe_split(bool on);
+bool pipe_split();
+// Whether the most recent stencil launch was a pipeline pass that split its
+// last group.
+bool last_pipe_split();
 // Fill-aware workgroup shares of the pipeline passes (chunk_schedule.hpp:
 // balanced_starts; default on): a share that crosses a column-group boundary
 // pays a second pipeline fill, and with equal row shares those workgroups set

@@ -59,9 +59,11 @@ constexpr int kLdsRows = 16;
 // tests assert that their shapes reach the kernel the benchmarks time).
 std::atomic<const char*> g_last_dispatch{"none"};
 std::atomic<bool> g_last_lag1{false};  // the pipeline launcher sets it after note()
+std::atomic<bool> g_last_split{false};  // likewise
 inline void note(const char* k) {
   g_last_dispatch.store(k, std::memory_order_relaxed);
   g_last_lag1.store(false, std::memory_order_relaxed);
+  g_last_split.store(false, std::memory_order_relaxed);
 }
 
 // Tuned on MI355X with bench/stencil_tune.hip (profiles/stencil_tuning/*.log):
@@ -376,6 +378,10 @@ std::atomic<bool> g_pipe_lag1{[] {
   const char* e = experiment_env("MXS_PIPE_LAG1");  // experiments build only
   return !(e && std::string(e) == "0");
 }()};
+std::atomic<bool> g_pipe_split{[] {
+  const char* e = experiment_env("MXS_PIPE_SPLIT");  // experiments build only
+  return !(e && std::string(e) == "0");
+}()};
 std::atomic<bool> g_pipe_balanced{[] {
   const char* e = experiment_env("MXS_PIPE_BALANCED");  // experiments build only
   return !(e && std::string(e) == "0");
@@ -388,23 +394,27 @@ bool pipe_joint() { return g_pipe_joint.load(std::memory_order_relaxed); }
 void set_pipe_lag1(bool on) { g_pipe_lag1.store(on, std::memory_order_relaxed); }
 bool pipe_lag1() { return g_pipe_lag1.load(std::memory_order_relaxed); }
 bool last_pipe_lag1() { return g_last_lag1.load(std::memory_order_relaxed); }
+void set_pipe_split(bool on) { g_pipe_split.store(on, std::memory_order_relaxed); }
+bool pipe_split() { return g_pipe_split.load(std::memory_order_relaxed); }
+bool last_pipe_split() { return g_last_split.load(std::memory_order_relaxed); }
 void set_pipe_balanced(bool on) { g_pipe_balanced.store(on, std::memory_order_relaxed); }
 bool pipe_balanced_on() { return g_pipe_balanced.load(std::memory_order_relaxed); }
 namespace detail {
 bool pipe_balanced() { return g_pipe_balanced.load(std::memory_order_relaxed); }
-void pipe_starts(index_t groups, index_t rows, int blocks, index_t fill, PipeShares* out) {
+void pipe_starts(index_t groups, index_t rows, int blocks, index_t fill, PipeShares* out, index_t last_rows) {
   struct Entry {
-    index_t groups, rows, fill;
+    index_t groups, rows, fill, last_rows;
     int blocks;
     std::vector<std::int64_t> start;
   };
   thread_local std::vector<Entry> cache;
   const Entry* hit = nullptr;
   for (const auto& e : cache)
-    if (e.groups == groups && e.rows == rows && e.fill == fill && e.blocks == blocks) hit = &e;
+    if (e.groups == groups && e.rows == rows && e.fill == fill && e.last_rows == last_rows && e.blocks == blocks)
+      hit = &e;
   if (!hit) {
     if (cache.size() >= 16) cache.erase(cache.begin());
-    cache.push_back(Entry{groups, rows, fill, blocks, balanced_starts(groups, rows, blocks, fill)});
+    cache.push_back(Entry{groups, rows, fill, last_rows, blocks, balanced_starts(groups, rows, blocks, fill, last_rows)});
     hit = &cache.back();
   }
   out->n = blocks;
@@ -412,6 +422,7 @@ void pipe_starts(index_t groups, index_t rows, int blocks, index_t fill, PipeSha
 }
 void note_dispatch(const char* k) { note(k); }
 void note_pipe_lag1(bool lag1) { g_last_lag1.store(lag1, std::memory_order_relaxed); }
+void note_pipe_split(bool split) { g_last_split.store(split, std::memory_order_relaxed); }
 }  // namespace detail
 
 #define MXS_INST_STENCIL(T)                                                                                    \

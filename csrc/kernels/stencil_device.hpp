@@ -1185,11 +1185,24 @@ struct JointShape {
   static_assert(OWG > 0, "time block too deep for a joint group");
 };
 
-template <typename B, int S0, int S1, int PF, bool WRAP, bool JOINT = false, int G = kWavesPerBlock, int LAG1 = 0>
+// SUB (joint windows): the chunk may be one of several sub-groups of gs <= G
+// strips that share the workgroup and its barriers (the split narrow group of
+// stencil5_stream_pipe_kernel). `strip` then counts within the sub-group, `ring`
+// points at the sub-group's first slot of the (G-strip) ring row, and the chunk
+// runs the blocks of a chunk of sync_rows >= ye - ys rows; the extra iterations
+// store nothing (the row term drops them) and read only clamped or wrapped
+// rows. ye == ys is allowed. The caller passes wave-uniform values as such
+// (wave_uniform): with a row range the compiler takes for per-lane, stage 0's
+// row stepping moves to the VALU (+5% VALU per row, and the pass then ends
+// 4% later, with the workgroups of the split group).
+template <typename B, int S0, int S1, int PF, bool WRAP, bool JOINT = false, int G = kWavesPerBlock, int LAG1 = 0,
+          bool SUB = false>
 __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in, typename B::T* __restrict__ out,
                                            index_t pitch, index_t core_off, index_t W, index_t H, index_t xw,
                                            index_t x_end, index_t ys, index_t ye, typename B::T c0, typename B::T c1,
-                                           typename B::V* __restrict__ ring, int stage, int strip = 0) {
+                                           typename B::V* __restrict__ ring, int stage, int strip = 0,
+                                           index_t sync_rows = 0, int gs = G) {
+  static_assert(!SUB || JOINT, "sub-groups are cut from joint windows");
   static_assert(PF % 3 == 0, "the window rotates through 3 slots: PF must be a multiple of 3");
   using P = PipeShape<S0, S1, PF>;
   constexpr int S = P::S, RING = P::RING;
@@ -1224,8 +1237,12 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
   constexpr int D = (PF - E0 % PF) % PF;
   constexpr int T1 = (E0 + D) / PF + 1;  // stage-1 start block (P::T1 for the default order)
   static_assert(ASC0 || T1 == P::T1, "stage-1 start block");
-  const index_t n_it0 = rows + 2 * S1 + E0 + D;  // stage 0: level-S0 rows [ys - S1, ye + S1)
-  const index_t n_it1 = rows + E1;               // stage 1: output rows [ys, ye)
+  const index_t brows = SUB ? sync_rows : rows;  // the rows that set the block count
+  // Valid columns of this (sub-)group's joint row and its output columns (JointShape, for gs strips).
+  const int span = SUB ? gs * J::OW0 : J::SPAN;
+  const int owg = SUB ? (span - 2 * J::A1 < gs * J::OW1 ? span - 2 * J::A1 : gs * J::OW1) : J::OWG;
+  const index_t n_it0 = brows + 2 * S1 + E0 + D;  // stage 0: level-S0 rows [ys - S1, ye + S1)
+  const index_t n_it1 = brows + E1;               // stage 1: output rows [ys, ye)
   const index_t blocks0 = (n_it0 + PF - 1) / PF, blocks1 = T1 + (n_it1 + PF - 1) / PF;
   const index_t blocks = blocks0 > blocks1 ? blocks0 : blocks1;
   // This lane's slot in a ring row, and the ring's row stride (lane vectors).
@@ -1235,7 +1252,7 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
     constexpr int AL0 = J::A0 / 4;  // stage-0 lanes per side without a valid level-S0 column
     if (stage == 0) {
       const bool valid = lane >= AL0 && lane < kWaveSize - AL0;
-      const int tail = J::SPAN / 4 + strip * 2 * AL0 + (lane < AL0 ? lane : lane - (kWaveSize - 2 * AL0));
+      const int tail = span / 4 + strip * 2 * AL0 + (lane < AL0 ? lane : lane - (kWaveSize - 2 * AL0));
       slot = valid ? strip * (J::OW0 / 4) + lane - AL0 : tail;
     } else {
       slot = strip * (J::OW1 / 4) + lane;
@@ -1370,7 +1387,7 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
       // [A1, A1 + OWG) (the last window may run past it); windows tile the group.
       constexpr int AL1 = J::A1 / 4;
       const int q = strip * J::OW1 + lane * N;  // joint-row column of this lane's first cell
-      store_lane = lane >= AL1 && lane < kWaveSize - AL1 && q + N <= J::A1 + J::OWG && gx < x_end;
+      store_lane = lane >= AL1 && lane < kWaveSize - AL1 && q + N <= J::A1 + owg && gx < x_end;
     } else {
       store_lane = lane >= AL && lane < kWaveSize - AL && gx < x_end && xw < x_end;
     }
@@ -1473,9 +1490,34 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
 // balanced_starts), start[w] .. start[w + 1] for workgroup w — passed by value
 // in the kernel arguments (2 KB), so a launch needs no device table and stays
 // graph-capturable.
+//
+// The split narrow group. A partial last group costs a whole one: all eight
+// waves stream every row of it whatever it stores (32768 columns at S = 24:
+// 36.25 groups of 904, and the 37th stores 224 columns). When what is left for
+// the last group fits a two-strip joint group (JointShape<S0, S1, 2>: 440
+// columns at 12 + 12), the workgroup runs it as two independent two-strip
+// sub-groups side by side: sub-group s = strip / 2 takes waves {strip % 2,
+// stage}, half s of every ring row and half s of the rows, so the group costs
+// half a group per row. In the linear space the group is split_half =
+// ceil(rows / 2) long, and a workgroup holding [a, b) of it runs rows [a, b)
+// on sub-group 0 and [a + half, min(b + half, rows)) on sub-group 1. Both take
+// the same barriers (pipe_chunk SUB: the block count of sub-group 0's rows,
+// never the fewer). Same operations per cell in the same order: bitwise equal
+// output. fp32 12 + 12 in the ascending order only (the headline pass).
+__device__ __forceinline__ int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ index_t wave_uniform(index_t v) {
+  const unsigned long long u = static_cast<unsigned long long>(v);
+  const unsigned lo = __builtin_amdgcn_readfirstlane(unsigned(u)), hi = __builtin_amdgcn_readfirstlane(unsigned(u >> 32));
+  return index_t((static_cast<unsigned long long>(hi) << 32) | lo);
+}
+template <typename T, int S0, int S1, int G, bool JOINT, int LAG1>
+constexpr bool pipe_split_form() {
+  return JOINT && sizeof(T) == 4 && G == 4 && S0 == 12 && S1 == 12 && LAG1 == 3;
+}
 constexpr int kMaxShareBlocks = 512;
 struct PipeShares {
   index_t share = 0;
+  index_t split_half = 0;  // > 0: the last group is split and this long in the linear space
   int n = 0;
   int start[kMaxShareBlocks + 1];
   static PipeShares equal(index_t share) {
@@ -1498,7 +1540,9 @@ __global__ __launch_bounds__(2 * G * kWaveSize) void stencil5_stream_pipe_kernel
   const index_t rows = y_end - y_begin;
   const index_t strips = (x_end - x_begin + OW - 1) / OW;
   const index_t groups = JOINT ? (x_end - x_begin + OWG - 1) / OWG : (strips + G - 1) / G;
-  const index_t total = groups * rows;
+  constexpr bool SPLIT = pipe_split_form<T, S0, S1, G, JOINT, LAG1>();
+  const index_t half = SPLIT ? shares.split_half : 0;
+  const index_t total = half > 0 ? (groups - 1) * rows + half : groups * rows;
   const int wave = threadIdx.x / kWaveSize;
   const int strip = wave % G, stage = wave / G;
   if constexpr (PRIO == 1) {
@@ -1527,15 +1571,35 @@ __global__ __launch_bounds__(2 * G * kWaveSize) void stencil5_stream_pipe_kernel
 #pragma unroll 1
   while (a < b) {  // workgroup-uniform: all 8 waves take every chunk (barriers inside)
     const index_t grp = a / rows, r0 = a - grp * rows;
+    if constexpr (SPLIT) {
+      if (half > 0 && grp == groups - 1) {  // workgroup-uniform
+        // The split narrow group: [r0, r1) of its half rows on sub-group 0, the
+        // same range of the other half on sub-group 1 (pieces per sub-group);
+        // each sub-group's joint row is its half of the ring row.
+        index_t r1 = half < r0 + (b - a) ? half : r0 + (b - a);
+        r1 = r1 - r0 > max_rows ? r0 + max_rows : r1;
+        // Wave-uniform, and told so: they depend on the wave's strip.
+        const int sub = wave_uniform(strip / 2), sstrip = wave_uniform(strip % 2);
+        const index_t q0 = wave_uniform(!sub ? r0 : r0 + half < rows ? r0 + half : rows);
+        const index_t q1 = wave_uniform(!sub ? r1 : r1 + half < rows ? r1 + half : rows);
+        using J = JointShape<S0, S1, G>;
+        static_assert(JointShape<S0, S1, G / 2>::ROW * 2 == J::ROW, "a sub-group's joint row is half the ring row");
+        pipe_chunk<B, S0, S1, PF, WRAP, true, G, LAG1, true>(in, out, pitch, core_off, W, H, x_begin + grp * OWG, x_end,
+                                                             y_begin + q0, y_begin + q1, c0, c1,
+                                                             ring + sub * (J::ROW / 2), stage, sstrip, r1 - r0, G / 2);
+        a += r1 - r0;
+        continue;
+      }
+    }
     index_t r1 = rows < r0 + (b - a) ? rows : r0 + (b - a);
     r1 = r1 - r0 > max_rows ? r0 + max_rows : r1;
     if constexpr (JOINT) {
       pipe_chunk<B, S0, S1, PF, WRAP, true, G, LAG1>(in, out, pitch, core_off, W, H, x_begin + grp * OWG, x_end,
-                                               y_begin + r0, y_begin + r1, c0, c1, ring, stage, strip);
+                                                     y_begin + r0, y_begin + r1, c0, c1, ring, stage, strip);
     } else {
       const index_t xw = x_begin + (grp * G + strip) * OW;
-      pipe_chunk<B, S0, S1, PF, WRAP, false, G, LAG1>(in, out, pitch, core_off, W, H, xw, x_end, y_begin + r0, y_begin + r1, c0, c1,
-                                      ring + strip * P::RING * kWaveSize, stage);
+      pipe_chunk<B, S0, S1, PF, WRAP, false, G, LAG1>(in, out, pitch, core_off, W, H, xw, x_end, y_begin + r0,
+                                                      y_begin + r1, c0, c1, ring + strip * P::RING * kWaveSize, stage);
     }
     a += r1 - r0;
   }

@@ -17,6 +17,7 @@ namespace detail {
 
 void note_dispatch(const char* kernel);  // stencil.hip: last_stencil_dispatch() record
 void note_pipe_lag1(bool lag1);          // stencil.hip: last_pipe_lag1() record
+void note_pipe_split(bool split);        // stencil.hip: last_pipe_split() record
 
 // fp64 depths the wide-lane pipeline takes (S0 = S/2, S1 = S - S0 <= 8 levels
 // per stage: the windows fit 2 waves/SIMD without spilling).
@@ -106,14 +107,37 @@ int pipe_blocks() {
   return std::max(1, blocks / gpu_share());
 }
 
-template <typename T, int S, bool WRAP, bool SUM, int JS0 = 0>
-index_t pipe_share(index_t x0, index_t x1, index_t y0, index_t y1) {
+template <typename T, int S, int JS0 = 0>
+index_t pipe_groups(index_t x0, index_t x1) {
   constexpr int OW = StripShape<T, S, true>::OW;
   constexpr int OWG = JointShape<(JS0 > 0 ? JS0 : S / 2), S - (JS0 > 0 ? JS0 : S / 2), kWavesPerBlock>::OWG;
-  const index_t groups =
-      JS0 > 0 ? (x1 - x0 + OWG - 1) / OWG : ((x1 - x0 + OW - 1) / OW + kWavesPerBlock - 1) / kWavesPerBlock;
+  return JS0 > 0 ? (x1 - x0 + OWG - 1) / OWG : ((x1 - x0 + OW - 1) / OW + kWavesPerBlock - 1) / kWavesPerBlock;
+}
+
+// Length of the split narrow last group in the linear (group x rows) space
+// (stencil_device.hpp: pipe_split_form), ceil(rows / 2), or 0 when the pass
+// does not split: another form, the switch off (kernels::set_pipe_split), or
+// more columns left for the last group than a two-strip joint group stores.
+template <typename T, int S, int JS0, int LAG1>
+index_t pipe_split_half(index_t x0, index_t x1, index_t y0, index_t y1) {
+  if constexpr (JS0 > 0) {
+    if constexpr (pipe_split_form<T, JS0, S - JS0, kWavesPerBlock, true, LAG1>()) {
+      constexpr int OWG = JointShape<JS0, S - JS0, kWavesPerBlock>::OWG;
+      constexpr int OWG2 = JointShape<JS0, S - JS0, 2>::OWG;
+      const index_t rem = (x1 - x0) - (pipe_groups<T, S, JS0>(x0, x1) - 1) * OWG;
+      if (pipe_split() && rem <= OWG2) return (y1 - y0 + 1) / 2;
+    }
+  }
+  return 0;
+}
+
+// Rows per workgroup of the linear space; split_half: pipe_split_half().
+template <typename T, int S, bool WRAP, bool SUM, int JS0 = 0>
+index_t pipe_share(index_t x0, index_t x1, index_t y0, index_t y1, index_t split_half = 0) {
+  const index_t groups = pipe_groups<T, S, JS0>(x0, x1);
   const int blocks = pipe_blocks<T, S, WRAP, SUM, JS0>();
-  return (groups * (y1 - y0) + blocks - 1) / blocks;
+  const index_t total = split_half > 0 ? (groups - 1) * (y1 - y0) + split_half : groups * (y1 - y0);
+  return (total + blocks - 1) / blocks;
 }
 
 // Row iterations a chunk of R rows costs beyond R (pipe_chunk: the longer of
@@ -130,7 +154,7 @@ constexpr index_t pipe_fill_rows() {
 
 // Fill-aware shares (balanced_starts), memoised per shape: the binary search
 // costs ~10 us of host time, a launch must not.
-void pipe_starts(index_t groups, index_t rows, int blocks, index_t fill, PipeShares* out);
+void pipe_starts(index_t groups, index_t rows, int blocks, index_t fill, PipeShares* out, index_t last_rows = 0);
 
 // MXS_PIPE_BALANCED=0: equal row shares (the round-2 rule), for comparison.
 bool pipe_balanced();
@@ -139,16 +163,17 @@ template <typename T, int S, bool WRAP, bool SUM, int JS0, int LAG1 = 0, int XB 
 void launch_pipe_form(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1, T c0,
                       T c1, T sc, hipStream_t s) {
   static_assert(XB == 0 || (SUM && XB == kScaledBody && JS0 > 0), "the scaled form runs the joint pipeline");
-  const index_t share = pipe_share<T, S, WRAP, SUM, JS0>(x0, x1, y0, y1);
+  // The same lengths in the share, the fill-aware starts and the kernel's own
+  // `total`: the narrow last group counts split_half rows when it is split.
+  const index_t split_half = pipe_split_half<T, S, JS0, LAG1>(x0, x1, y0, y1);
+  const index_t share = pipe_share<T, S, WRAP, SUM, JS0>(x0, x1, y0, y1, split_half);
   const int blocks = pipe_blocks<T, S, WRAP, SUM, JS0>();
   PipeShares shares = PipeShares::equal(share);
+  shares.split_half = split_half;
   if (pipe_balanced() && blocks <= kMaxShareBlocks) {
     constexpr int S0 = JS0 > 0 ? JS0 : pipe_s0<T, S, SUM>();
-    constexpr int OW = StripShape<T, S, true>::OW;
-    constexpr int OWG = JointShape<(JS0 > 0 ? JS0 : S / 2), S - (JS0 > 0 ? JS0 : S / 2), kWavesPerBlock>::OWG;
-    const index_t groups =
-        JS0 > 0 ? (x1 - x0 + OWG - 1) / OWG : ((x1 - x0 + OW - 1) / OW + kWavesPerBlock - 1) / kWavesPerBlock;
-    pipe_starts(groups, y1 - y0, blocks, pipe_fill_rows<S0, S - S0, pipe_pf<T, S>(), LAG1>(), &shares);
+    pipe_starts(pipe_groups<T, S, JS0>(x0, x1), y1 - y0, blocks, pipe_fill_rows<S0, S - S0, pipe_pf<T, S>(), LAG1>(),
+                &shares, split_half);
   }
   // Shares longer than kMaxChunkBytes are walked in pieces inside the kernel;
   // a piece must still hold a useful number of rows.
@@ -161,6 +186,7 @@ void launch_pipe_form(const T* in, T* out, const TileGeom& g, index_t x0, index_
       in, out, g.pitch, g.core_offset(), g.width, g.height, x0, x1, y0, y1, shares, SUM ? sc : c0, kc);
   note_dispatch(XB == kScaledBody ? "stream_pipe_scaled" : SUM ? "stream_pipe_sum" : "stream_pipe");
   note_pipe_lag1(LAG1 != 0);
+  note_pipe_split(split_half > 0);
 }
 
 template <typename T, int S, bool WRAP, bool SUM, int XB = 0>

@@ -238,7 +238,9 @@ PYBIND11_MODULE(_mxs_core, m) {
       "(HOLD_* bits; left / right to whole `vec`-cell vectors), and the frame rectangles that cover the rest "
       "(kernels/fixed_edge_split.hpp); an empty interior is (0, 0, 0, 0)");
   m.def("balanced_starts", &kernels::balanced_starts, py::arg("groups"), py::arg("rows"), py::arg("blocks"),
-        py::arg("fill"), "fill-aware linear starts of the pipeline workgroups' shares (blocks + 1 entries)");
+        py::arg("fill"), py::arg("last_rows") = 0,
+        "fill-aware linear starts of the pipeline workgroups' shares (blocks + 1 entries); last_rows > 0: the last "
+        "group's run is that long (the split narrow group), 0 = rows");
   // Interior-first (halo-last) schedule of the multi-GPU opening super-step.
   m.def(
       "halo_last_schedule",

@@ -180,6 +180,12 @@ PYBIND11_MODULE(_mxs_hip, m) {
   m.def("set_pipe_lag1", &kernels::set_pipe_lag1, py::arg("on"),
         "ascending level order in the joint fp32 pipeline where it pays (default on; bitwise equal output)");
   m.def("pipe_lag1", &kernels::pipe_lag1);
+  m.def("set_pipe_split", &kernels::set_pipe_split, py::arg("on"),
+        "split a narrow last column group of the fp32 S = 24 pass into two half-height sub-groups (default on; "
+        "bitwise equal output)");
+  m.def("pipe_split", &kernels::pipe_split);
+  m.def("last_pipe_split", &kernels::last_pipe_split,
+        "whether the most recent stencil launch was a pipeline pass that split its last group");
   m.def("set_pipe_balanced", &kernels::set_pipe_balanced, py::arg("on"),
         "fill-aware workgroup shares in the pipeline passes (default on; bitwise equal output)");
   m.def("pipe_balanced", &kernels::pipe_balanced_on);

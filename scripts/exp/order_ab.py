@@ -1,16 +1,20 @@
-"""Level order A/B in the bench's own window (round 6: ascending at every share
-length vs the round-5 rule, descending on shares past 768 rows).
+"""Pipeline switch A/B in the bench's own window. --ab order (round 6): the
+level order, ascending at every share length vs the round-5 rule, descending on
+shares past 768 rows. --ab split: the narrow last column group of the S = 24
+pass run as two half-height sub-groups (hip().set_pipe_split) vs as one whole
+group.
 
-One process, one solver per tile; each round sets the order
-(hip().set_pipe_lag1: on = ascending everywhere, off = descending everywhere),
-runs ~200 ms of warm passes and a drained warm pass, then times one window as
+One process, one solver per tile; each round sets the switch
+(order: hip().set_pipe_lag1, on = ascending everywhere, off = descending
+everywhere; split: hip().set_pipe_split), runs ~200 ms of warm passes and a drained warm pass, then times one window as
 bench.py does (host clock, enqueue to drained + device sync) with clock stamps
 around it: wall ms, the pass's shader cycles at the slowest XCD's clock and
 the median clock. The order alternates first/second from round to round.
-Prints per tile the paired ratios asc / desc (median, notch) of wall time and
-of cycles.
+Prints per tile the paired ratios on / off (asc / desc, split / whole: median,
+notch) of wall time and of cycles.
 
-usage: python scripts/exp/order_ab.py [--tiles 32768x32768,16384x16384] [--rounds 12] [--steps 20]
+usage: python scripts/exp/order_ab.py [--ab order|split] [--tiles 32768x32768,16384x16384] [--rounds 12]
+                                      [--steps 20] [--time-block 0]
 """
 import argparse
 import json
@@ -42,21 +46,27 @@ def main() -> int:
     p.add_argument("--tiles", default="32768x32768,16384x16384")
     p.add_argument("--rounds", type=int, default=12)
     p.add_argument("--steps", type=int, default=20)
+    p.add_argument("--ab", default="order", choices=["order", "split"])
+    p.add_argument("--time-block", type=int, default=0, help="the solver's time block (0 = auto)")
     args = p.parse_args()
     H = hip()
+    on, off = ("asc", "desc") if args.ab == "order" else ("split", "whole")
+    set_switch = H.set_pipe_lag1 if args.ab == "order" else H.set_pipe_split
+    switch_used = H.last_pipe_lag1 if args.ab == "order" else H.last_pipe_split
     K = H.clock_stamp_slots()
     khz = H.wall_clock_rate_khz()
     stamps = torch.zeros(6 * K, dtype=torch.int64, device="cuda")
     s = torch.cuda.current_stream().cuda_stream
     for tile in args.tiles.split(","):
         w, h = (int(v) for v in tile.split("x"))
-        st = Stencil2D(StencilConfig(global_width=w, global_height=h, dims="1x1", dtype="f32"))
+        st = Stencil2D(StencilConfig(global_width=w, global_height=h, dims="1x1", dtype="f32",
+                                     time_block=args.time_block))
         st.run(args.steps)
         st.prepare(args.steps)
         res = {True: [], False: []}
         for r in range(args.rounds):
             for lag in ((True, False) if r % 2 == 0 else (False, True)):
-                H.set_pipe_lag1(lag)
+                set_switch(lag)
                 st.warm(args.steps, 0.2, 1)
                 st.synchronize()
                 torch.cuda.synchronize()
@@ -67,7 +77,7 @@ def main() -> int:
                 st.synchronize()
                 torch.cuda.synchronize()
                 wall = (time.perf_counter() - t0) * 1e3
-                used = bool(H.last_pipe_lag1())
+                used = bool(switch_used())
                 H.clock_stamp(stamps.data_ptr() + 3 * K * 8, s)
                 torch.cuda.synchronize()
                 v = stamps.cpu().view(2, K, 3).tolist()
@@ -80,18 +90,18 @@ def main() -> int:
                 slow = min(statistics.median(m) for m in per.values())
                 med = statistics.median([m for ms in per.values() for m in ms])
                 res[lag].append({"wall_ms": wall, "kcycles_slowest": wall * 1e3 * slow / 1e3, "mhz": med,
-                                 "mhz_slowest": slow, "lag1_used": used})
-        H.set_pipe_lag1(True)
+                                 "mhz_slowest": slow, "used": used})
+        set_switch(True)
         a, d = res[True], res[False]
-        rec = {"tile": tile, "steps": args.steps, "rounds": args.rounds,
-               "asc_wall_ms": round(statistics.median(x["wall_ms"] for x in a), 4),
-               "desc_wall_ms": round(statistics.median(x["wall_ms"] for x in d), 4),
-               "asc_mhz": round(statistics.median(x["mhz"] for x in a)),
-               "desc_mhz": round(statistics.median(x["mhz"] for x in d)),
-               "wall_asc_over_desc": notch([x["wall_ms"] / y["wall_ms"] for x, y in zip(a, d)]),
-               "kcycles_asc_over_desc": notch([x["kcycles_slowest"] / y["kcycles_slowest"] for x, y in zip(a, d)]),
-               "mhz_asc_over_desc": notch([x["mhz"] / y["mhz"] for x, y in zip(a, d)]),
-               "orders_used": [all(x["lag1_used"] for x in a), not any(x["lag1_used"] for x in d)],
+        rec = {"ab": args.ab, "tile": tile, "time_block": st.time_block, "steps": args.steps, "rounds": args.rounds,
+               f"{on}_wall_ms": round(statistics.median(x["wall_ms"] for x in a), 4),
+               f"{off}_wall_ms": round(statistics.median(x["wall_ms"] for x in d), 4),
+               f"{on}_mhz": round(statistics.median(x["mhz"] for x in a)),
+               f"{off}_mhz": round(statistics.median(x["mhz"] for x in d)),
+               f"wall_{on}_over_{off}": notch([x["wall_ms"] / y["wall_ms"] for x, y in zip(a, d)]),
+               f"kcycles_{on}_over_{off}": notch([x["kcycles_slowest"] / y["kcycles_slowest"] for x, y in zip(a, d)]),
+               f"mhz_{on}_over_{off}": notch([x["mhz"] / y["mhz"] for x, y in zip(a, d)]),
+               "switch_used": [all(x["used"] for x in a), not any(x["used"] for x in d)],
                "kernel": H.last_stencil_dispatch()}
         print(json.dumps(rec), flush=True)
         del st
