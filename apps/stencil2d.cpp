@@ -36,6 +36,8 @@
 // --loopback, --bind bunch|rrobin,
 // --dump / --no-dump, --checksum, --non-periodic, --block-fixed-edges (with --non-periodic: keep the time
 // block, the frame along the fixed edges on the held-side kernel), --seed S, --json FILE,
+// --tol T [--check-every N] (iterate until the linf residual A u - u is <= T, checked every N iterations,
+// default 16 time blocks, with --iters as the cap; prints "converged after K iterations, residual R (linf)"),
 // --checkpoint FILE / --resume FILE (collective MPI-IO global grid file, any
 // decomposition; same format as stencil2d_cpu and the Python package),
 // --comm-timeout SECONDS (halo watchdog, default 300), --fault-inject
@@ -46,6 +48,7 @@
 #include <cmath>
 #include <fstream>
 #include <iostream>
+#include <limits>
 #include <memory>
 #include <sstream>
 #include <vector>
@@ -236,23 +239,80 @@ int run(MpiEnv& env, const Cli& cli, const CartTopology& topo, const DeviceBindi
       if (solver) solver->synchronize();
       init_stream.sync();
     };
+    // --tol T [--check-every N]: iterate until the agreed linf residual (the
+    // change the next step would make) is <= T, with --iters as the cap. The
+    // solver backends run StencilSolver::run_until; the mpi-staged loop checks
+    // the same way (exchange, residual kernel, MPI reductions), so every
+    // backend stops at the same iteration.
+    const bool until = cli.has("tol");
+    const double tol = cli.get_double("tol", 0.0);
+    MXS_CHECK(!until || tol >= 0.0, "--tol must be >= 0, got " << tol);
+    const long long check_every = cli.get_int("check-every", 0);
+    MXS_CHECK(check_every >= 0, "--check-every must be >= 0, got " << check_every);
+    RunUntil conv;
+    DeviceBuffer<double> res_buf;
+    DeviceBuffer<unsigned> res_counter;
+    auto staged_residual = [&]() {  // collective: linf of A u - u over all ranks
+      const index_t grid = kernels::residual_grid_size(g);
+      if (res_buf.size() < 2 + 2 * grid) res_buf.reset(2 + 2 * grid);
+      if (!res_counter.get()) res_counter.reset(1);
+      auto* norms = reinterpret_cast<kernels::ResidualNorms*>(res_buf.get());
+      staged->exchange(cur, init_stream.get());
+      kernels::stencil5_residual<T>(cur, g, cfg.coeffs, norms, res_buf.get() + 2, res_counter.get(), init_stream.get());
+      kernels::ResidualNorms h{0.0, 0.0};
+      MXS_HIP_CHECK(hipMemcpyAsync(&h, norms, sizeof(h), hipMemcpyDeviceToHost, init_stream.get()));
+      init_stream.sync();
+      return env.max_over_ranks(std::isfinite(h.linf) ? h.linf : std::numeric_limits<double>::infinity());
+    };
+    auto steps_until = [&]() {
+      if (solver && !fault.armed()) {
+        conv = solver->run_until(tol, int(iters), int(check_every));
+        return;
+      }
+      const long long every = check_every > 0 ? check_every : (long long)kDefaultCheckBlocks * time_block;
+      for (;;) {
+        conv.residual = solver ? solver->residual().linf : staged_residual();
+        ++conv.checks;
+        if (!std::isfinite(conv.residual)) {
+          conv.reason = "non-finite residual";
+          break;
+        }
+        if (conv.residual <= tol) {
+          conv.converged = true;
+          conv.reason = "converged: linf residual <= tol";
+          break;
+        }
+        if (conv.iterations >= iters) {
+          conv.reason = "max_iters reached";
+          break;
+        }
+        const long long n = std::min<long long>(every, iters - conv.iterations);
+        steps(n);
+        conv.iterations += int(n);
+      }
+    };
     const long long warmup = cli.get_int("warmup", 10);
     steps(warmup);
-    if (solver && !fault.armed()) solver->prepare(int(iters));  // graphs + first launches, untimed
+    if (solver && !fault.armed()) {  // graphs + first launches, untimed
+      const long long chunk = check_every > 0 ? check_every : (long long)kDefaultCheckBlocks * solver->time_block();
+      solver->prepare(int(until ? std::max<long long>(1, std::min(chunk, iters)) : iters));
+    }
     sync();
     env.barrier();
     const double t0 = MPI_Wtime();
-    steps(iters);
+    if (until) steps_until();
+    else steps(iters);
     sync();
     env.barrier();
     const double dt = env.max_over_ranks(MPI_Wtime() - t0);
+    const long long ran = until ? conv.iterations : iters;
     if (solver) cur = solver->current();
     if (cli.has("checkpoint")) {
       std::vector<T> h;
       copy_tile_to_host(h, cur, g);
-      write_grid_file<T>(MPI_COMM_WORLD, cli.get("checkpoint"), h.data(), g, blk, start_iter + warmup + iters, seed);
+      write_grid_file<T>(MPI_COMM_WORLD, cli.get("checkpoint"), h.data(), g, blk, start_iter + warmup + ran, seed);
     }
-    const double gcells = double(gw) * double(gh) * double(iters) / dt / 1e9;
+    const double gcells = double(gw) * double(gh) * double(ran) / dt / 1e9;
     double checksum = std::nan("");
     const bool want_sum = cli.has("checksum") ? cli.flag("checksum") : (lw * lh <= (index_t(1) << 24));
     if (want_sum) {
@@ -266,7 +326,7 @@ int run(MpiEnv& env, const Cli& cli, const CartTopology& topo, const DeviceBindi
     if (rank == 0) {
       std::ostringstream js;
       js << "{\"app\": \"stencil2d\", \"metric\": \"gcells_per_s\", \"value\": " << app::fmt(gcells)
-         << ", \"ms_per_iter\": " << app::fmt(dt / double(iters) * 1e3) << ", \"ranks\": " << env.size()
+         << ", \"ms_per_iter\": " << app::fmt(dt / double(std::max<long long>(ran, 1)) * 1e3) << ", \"ranks\": " << env.size()
          << ", \"dims\": \"" << topo.rows << "x" << topo.cols << "\", \"global\": \"" << gw << "x" << gh
          << "\", \"dtype\": \"" << (sizeof(T) == 4 ? "f32" : "f64") << "\", \"backend\": \"" << backend
          << "\", \"graph\": \"" << (solver ? solver->graph_status() : std::string("n/a"))
@@ -279,8 +339,18 @@ int run(MpiEnv& env, const Cli& cli, const CartTopology& topo, const DeviceBindi
         if (!solver->direct_state().empty()) js << ", \"direct_halo\": \"" << solver->direct_state() << "\"";
         if (!solver->fixed_edge_note().empty()) js << ", \"fixed_edges\": \"" << solver->fixed_edge_note() << "\"";
       }
+      if (until)
+        js << ", \"tol\": " << app::fmt(tol) << ", \"converged\": " << (conv.converged ? "true" : "false")
+           << ", \"iterations\": " << conv.iterations << ", \"residual\": " << app::fmt(conv.residual)
+           << ", \"checks\": " << conv.checks << ", \"wall_s\": " << app::fmt(dt);
       if (want_sum) js << ", \"checksum\": " << app::fmt(checksum);
       js << app::meta_json(device_description(dev.device)) << "}";
+      if (until && conv.converged)
+        std::cout << "converged after " << conv.iterations << " iterations, residual " << app::fmt(conv.residual)
+                  << " (linf)" << '\n';
+      else if (until)
+        std::cout << "not converged after " << conv.iterations << " iterations, residual " << app::fmt(conv.residual)
+                  << '\n';
       std::cout << "Gcells/s: " << app::fmt(gcells) << '\n';
       if (want_sum) std::cout << "checksum: " << app::fmt(checksum) << '\n';
       std::cout << js.str() << std::endl;

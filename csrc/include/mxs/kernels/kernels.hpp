@@ -9,6 +9,7 @@
 //   K11/12 copy2d_batch (halo pack/unpack/self)  kernels/halo.hip
 //   K2/4/5/8 dot_atomic, dot_partials, reduce_partials, dot_single_pass, dot_racy
 //                                                kernels/dot.hip
+//          stencil5_residual (norms of A u - u)  kernels/residual.hip
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -234,6 +235,31 @@ void stencil5_chunk_pass(const T* in, T* out, const TileGeom& g, const Stencil5C
 // any element is NaN): the range check of the sum form.
 template <typename T>
 void absmax(const T* x, index_t n, T* out, hipStream_t s);
+// ------------------------------------------------- residual norms (kernels/residual.hip)
+// For the Jacobi update u' = A u the residual r = A u - u is exactly the change
+// the next single step would make. Over the core of a ghost-ring tile, per cell
+//   r = fma(c_neighbor, (n + s) + (w + e), c_center * v) - v
+// in the element type (the stencil kernels' expression and order, then one
+// subtraction), reduced to linf = max |r| (NaN if any r is NaN) and sumsq =
+// sum r^2 accumulated in double. Reads only the core and the ring cells beside
+// it (row -1, row height, column -1, column width): deeper ring layers, the
+// four outside corners and the alignment padding never influence the result.
+// One streaming read, no write to the tile. Deterministic: the same input gives
+// the same bits in both outputs on every call (per-workgroup partials, a
+// last-block finish in a fixed order; the grid depends only on the geometry and
+// the CU count). sum_form / range of the coefficients are ignored.
+struct ResidualNorms {  // device layout: what the kernel leaves in *out
+  double linf;
+  double sumsq;
+};
+// Workgroups of the launch at most (either element type): `partials` holds
+// 2 * residual_grid_size(g) doubles, `counter` one unsigned (zeroed by the
+// launcher every call, as for dot).
+int residual_grid_size(const TileGeom& g);
+template <typename T>
+void stencil5_residual(const T* u, const TileGeom& g, Stencil5Coeffs c, ResidualNorms* out, double* partials,
+                       unsigned* counter, hipStream_t s);
+
 // Whether work on stream b runs while a kernel on stream a still runs (the two
 // sit on different hardware queues): one bounded ~0.8 ms sleeping wave on a, a
 // no-op kernel on b (kernels/queue_probe.hip). Synchronises both streams.

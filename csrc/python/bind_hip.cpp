@@ -166,6 +166,7 @@ PYBIND11_MODULE(_mxs_hip, m) {
       py::arg("width"), py::arg("height"), py::arg("dtype") = "f32", py::arg("sum_form") = true,
       "measured default Jacobi steps per pass / halo exchange for a tile");
   m.attr("MAX_TIME_BLOCK") = kernels::kMaxTimeBlock;
+  m.attr("DEFAULT_CHECK_BLOCKS") = kDefaultCheckBlocks;
   m.attr("MAX_TIME_BLOCK_DEEP") = kernels::kMaxTimeBlockDeep;
   m.def(
       "last_stencil_dispatch", [] { return std::string(kernels::last_stencil_dispatch()); },
@@ -207,6 +208,62 @@ PYBIND11_MODULE(_mxs_hip, m) {
         return r;
       },
       py::arg("x"), py::arg("n"), py::arg("dtype") = "f32", "max |x[i]| (device reduction; NaN if any is NaN)");
+  m.def(
+      "stencil5_residual",
+      [](std::uintptr_t x, const TileGeom& g, double c0, double c1, const std::string& dt, std::uintptr_t s) {
+        kernels::Stencil5Coeffs c{c0, c1};
+        const index_t grid = kernels::residual_grid_size(g);
+        DeviceBuffer<double> buf(2 + 2 * grid);
+        DeviceBuffer<unsigned> counter(1);
+        auto* norms = reinterpret_cast<kernels::ResidualNorms*>(buf.get());
+        if (parse_dtype(dt) == DType::F32)
+          kernels::stencil5_residual<float>(ptr<float>(x), g, c, norms, buf.get() + 2, counter.get(), strm(s));
+        else
+          kernels::stencil5_residual<double>(ptr<double>(x), g, c, norms, buf.get() + 2, counter.get(), strm(s));
+        kernels::ResidualNorms h{0.0, 0.0};
+        MXS_HIP_CHECK(hipMemcpyAsync(&h, norms, sizeof(h), hipMemcpyDeviceToHost, strm(s)));
+        MXS_HIP_CHECK(hipStreamSynchronize(strm(s)));
+        return py::make_tuple(h.linf, h.sumsq);
+      },
+      py::arg("src"), py::arg("geom"), py::arg("c_center") = 0.2, py::arg("c_neighbor") = 0.2,
+      py::arg("dtype") = "f32", py::arg("stream") = 0,
+      "(max |r|, sum r^2) of the Jacobi residual r = A u - u over the core of a ghost-ring tile "
+      "(reads the core and the ring cells beside it only; synchronises the stream)");
+  m.def(
+      "residual_kernel_times",
+      [](std::uintptr_t x, const TileGeom& g, double c0, double c1, const std::string& dt, int reps) {
+        // Measurements: `reps` event-timed pairs (stencil5_residual on the tile,
+        // absmax over the same buffer), scratch allocated once, one stream.
+        kernels::Stencil5Coeffs c{c0, c1};
+        const bool f32 = parse_dtype(dt) == DType::F32;
+        const index_t grid = kernels::residual_grid_size(g);
+        DeviceBuffer<double> buf(2 + 2 * grid), amax(1);
+        DeviceBuffer<unsigned> counter(1);
+        auto* norms = reinterpret_cast<kernels::ResidualNorms*>(buf.get());
+        Stream st(true, 0);
+        Event e0(true), e1(true), e2(true);
+        py::list res, abs;
+        for (int i = 0; i < reps; ++i) {
+          e0.record(st.get());
+          if (f32) kernels::stencil5_residual<float>(ptr<float>(x), g, c, norms, buf.get() + 2, counter.get(), st.get());
+          else kernels::stencil5_residual<double>(ptr<double>(x), g, c, norms, buf.get() + 2, counter.get(), st.get());
+          e1.record(st.get());
+          if (f32) kernels::absmax<float>(ptr<float>(x), g.alloc_elems(), reinterpret_cast<float*>(amax.get()), st.get());
+          else kernels::absmax<double>(ptr<double>(x), g.alloc_elems(), amax.get(), st.get());
+          e2.record(st.get());
+          MXS_HIP_CHECK(hipStreamSynchronize(st.get()));
+          res.append(double(e1.since(e0)));
+          abs.append(double(e2.since(e1)));
+        }
+        py::dict d;
+        d["residual_ms"] = res;
+        d["absmax_ms"] = abs;
+        d["workgroups"] = grid;
+        return d;
+      },
+      py::arg("src"), py::arg("geom"), py::arg("c_center") = 0.2, py::arg("c_neighbor") = 0.2,
+      py::arg("dtype") = "f32", py::arg("reps") = 20,
+      "measurements: event-timed (residual, absmax) kernel pairs over one tile, ms per launch");
   m.def(
       "stencil5_chunk_pass",
       [](std::uintptr_t in, std::uintptr_t out, const TileGeom& g, int steps, double c0, double c1,
@@ -697,6 +754,47 @@ PYBIND11_MODULE(_mxs_hip, m) {
           py::arg("iters"), py::arg("passes"), py::call_guard<py::gil_scoped_release>(),
           "untimed state-preserving passes of run(iters)'s shapes (sustained clocks before a short window)")
       .def("exchange_only", [](SolverHandle& h) { h.visit([](auto& s) { s.exchange_only(); }); })
+      .def(
+          "residual",
+          [](SolverHandle& h) {
+            Residual r;
+            {
+              py::gil_scoped_release nogil;
+              r = h.visit([](auto& s) { return s.residual(); });
+            }
+            py::dict d;
+            d["linf"] = r.linf;
+            d["l2"] = r.l2;
+            d["cells"] = r.cells;
+            return d;
+          },
+          "collective: norms of the Jacobi residual r = A u - u over the global core (the change the next "
+          "single step would make), agreed over ranks; the field is unchanged")
+      .def(
+          "run_until",
+          [](SolverHandle& h, double tol, int max_iters, int check_every, const std::string& norm) {
+            if (norm != "linf" && norm != "l2") throw std::invalid_argument("norm must be linf or l2, got '" + norm + "'");
+            const Norm n = norm == "l2" ? Norm::L2 : Norm::Linf;
+            RunUntil r;
+            {
+              py::gil_scoped_release nogil;
+              r = h.visit([&](auto& s) { return s.run_until(tol, max_iters, check_every, n); });
+            }
+            py::dict d;
+            d["converged"] = r.converged;
+            d["iterations"] = r.iterations;
+            d["residual"] = r.residual;
+            d["checks"] = r.checks;
+            d["reason"] = r.reason;
+            d["norm"] = norm;
+            py::list hist;
+            for (const auto& [it, linf, l2] : r.history) hist.append(py::make_tuple(it, linf, l2));
+            d["history"] = hist;
+            return d;
+          },
+          py::arg("tol"), py::arg("max_iters"), py::arg("check_every") = 0, py::arg("norm") = "linf",
+          "collective: run(check_every) + residual() until the agreed norm is <= tol, max_iters iterations ran or "
+          "the norm is not finite (check_every = 0: DEFAULT_CHECK_BLOCKS x time_block)")
       .def("synchronize", [](SolverHandle& h) { h.visit([](auto& s) { s.synchronize(); }); },
            py::call_guard<py::gil_scoped_release>())
       .def("current",

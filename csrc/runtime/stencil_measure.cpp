@@ -1,6 +1,6 @@
 // StencilSolver's prepare()-time measurements and the collective decisions
 // taken from them (the solver's schedules themselves: stencil_solver.cpp):
-//   * agree_max / device_barrier: the agreement and release primitives;
+//   * agree_max / agree_sum / device_barrier: the agreement and release primitives;
 //   * choose_opening: serial vs interior-first opening (three outer sets);
 //   * choose_steady: the super-steps after an interior-first opening;
 //   * validate_direct: the device-initiated push, bitwise then timed;
@@ -37,6 +37,16 @@ constexpr int kXcds = 8;
 
 template <typename T>
 void StencilSolver<T>::agree_max(std::vector<double>& v, const char* phase) {
+  agree(v, phase, false);
+}
+
+template <typename T>
+void StencilSolver<T>::agree_sum(std::vector<double>& v, const char* phase) {
+  agree(v, phase, true);
+}
+
+template <typename T>
+void StencilSolver<T>::agree(std::vector<double>& v, const char* phase, bool sum) {
   if (world_ <= 1 || v.empty()) return;
   if (cfg_.bootstrap) {  // the host allgather: the path the one-GPU multi-rank tests run too
     std::string blob(v.size() * sizeof(double), '\0');
@@ -49,12 +59,13 @@ void StencilSolver<T>::agree_max(std::vector<double>& v, const char* phase) {
     }
     MXS_CHECK(int(parts.size()) == world_, phase << ": host agreement returned " << parts.size() << " of "
                                                  << world_ << " ranks");
+    if (sum) std::fill(v.begin(), v.end(), 0.0);  // every rank's part, its own included, in rank order
     for (const auto& p : parts) {
       MXS_CHECK(p.size() == blob.size(), phase << ": ranks disagree on the agreement's length");
       for (size_t i = 0; i < v.size(); ++i) {
         double x;
         std::memcpy(&x, p.data() + i * sizeof(double), sizeof(double));
-        v[i] = std::max(v[i], x);
+        v[i] = sum ? v[i] + x : std::max(v[i], x);
       }
     }
     return;
@@ -64,7 +75,8 @@ void StencilSolver<T>::agree_max(std::vector<double>& v, const char* phase) {
   if (agree_buf_.size() < index_t(v.size())) agree_buf_.reset(index_t(v.size()));
   const size_t bytes = v.size() * sizeof(double);
   MXS_HIP_CHECK(hipMemcpyAsync(agree_buf_.get(), v.data(), bytes, hipMemcpyHostToDevice, main_.get()));
-  comm_->allreduce_max<double>(agree_buf_.get(), agree_buf_.get(), v.size(), main_.get());
+  if (sum) comm_->allreduce_sum<double>(agree_buf_.get(), agree_buf_.get(), v.size(), main_.get());
+  else comm_->allreduce_max<double>(agree_buf_.get(), agree_buf_.get(), v.size(), main_.get());
   MXS_HIP_CHECK(hipMemcpyAsync(v.data(), agree_buf_.get(), bytes, hipMemcpyDeviceToHost, main_.get()));
   wait_idle(phase);
 }
@@ -686,6 +698,8 @@ WindowPhases StencilSolver<T>::profile_window(int iters) {
 // instantiated in stencil_solver.cpp).
 #define MXS_MEASURE_INSTANTIATE(T)                                                                            \
   template void StencilSolver<T>::agree_max(std::vector<double>&, const char*);                              \
+  template void StencilSolver<T>::agree_sum(std::vector<double>&, const char*);                              \
+  template void StencilSolver<T>::agree(std::vector<double>&, const char*, bool);                            \
   template void StencilSolver<T>::device_barrier(const char*);                                               \
   template void StencilSolver<T>::rccl_barrier(const RcclComm*, const char*);                                \
   template void StencilSolver<T>::choose_opening(int);                                                       \

@@ -887,6 +887,91 @@ void StencilSolver<T>::exchange_only() {
 }
 
 template <typename T>
+Residual StencilSolver<T>::residual() {
+  MXS_TRACE_RANGE("stencil.residual");
+  MXS_CHECK(cfg_.kind == StencilKind::Jacobi5,
+            "residual: only the 5-point Jacobi solver has a residual (this solver runs the box stencil)");
+  maybe_stall("residual");
+  // The collective part first: with peers every rank exchanges, whatever it
+  // believes about its own ring (field_changed() is per rank).
+  // The direct halo refreshes the ring as a run's opening does (push the
+  // current bands, wait for the neighbours'): the same values, and the
+  // agreement below is past every rank's kernel before the next push.
+  if (direct_on_) {
+    join_side();
+    direct_->push(cur_, main_.get());
+    direct_->wait(main_.get());
+  } else if (multi_rank_ || !ghost_fresh_) {
+    exchange_only();
+  } else {
+    join_side();
+  }
+  const index_t grid = kernels::residual_grid_size(tile_);
+  const index_t need = 2 + 2 * grid;  // ResidualNorms, then two doubles per workgroup
+  if (residual_buf_.size() < need) residual_buf_.reset(need);
+  if (!residual_counter_.get()) residual_counter_.reset(1);
+  auto* norms = reinterpret_cast<kernels::ResidualNorms*>(residual_buf_.get());
+  kernels::stencil5_residual<T>(cur_, tile_, cfg_.coeffs, norms, residual_buf_.get() + 2, residual_counter_.get(),
+                                main_.get());
+  kernels::ResidualNorms h{0.0, 0.0};
+  MXS_HIP_CHECK(hipMemcpyAsync(&h, norms, sizeof(h), hipMemcpyDeviceToHost, main_.get()));
+  wait_idle("residual");
+  Residual r;
+  r.linf = h.linf;
+  double sumsq = h.sumsq;
+  r.cells = tile_.width * tile_.height;
+  if (world_ > 1) {
+    // max() of a NaN depends on the argument order: a non-finite local norm
+    // travels as +inf, so every rank sees the same (non-finite) result.
+    std::vector<double> mx{std::isfinite(h.linf) ? h.linf : std::numeric_limits<double>::infinity()};
+    std::vector<double> sm{sumsq, double(r.cells)};
+    agree_max(mx, "residual: linf agreement");
+    agree_sum(sm, "residual: l2 agreement");
+    r.linf = mx[0];
+    sumsq = sm[0];
+    r.cells = index_t(sm[1]);
+  }
+  r.l2 = std::sqrt(sumsq);
+  return r;
+}
+
+template <typename T>
+RunUntil StencilSolver<T>::run_until(double tol, int max_iters, int check_every, Norm norm) {
+  MXS_TRACE_RANGE("stencil.run_until");
+  MXS_CHECK(cfg_.kind == StencilKind::Jacobi5,
+            "run_until: only the 5-point Jacobi solver has a residual (this solver runs the box stencil)");
+  MXS_CHECK(tol >= 0.0, "run_until: tol must be >= 0, got " << tol);
+  MXS_CHECK(max_iters >= 0, "run_until: max_iters must be >= 0, got " << max_iters);
+  MXS_CHECK(check_every >= 0, "run_until: check_every must be >= 0 (0: " << kDefaultCheckBlocks << " x time_block), got " << check_every);
+  const int every = check_every > 0 ? check_every : kDefaultCheckBlocks * block_;
+  const char* name = norm == Norm::Linf ? "linf" : "l2";
+  RunUntil out;
+  for (;;) {
+    const Residual r = residual();
+    ++out.checks;
+    out.residual = norm == Norm::Linf ? r.linf : r.l2;
+    if (int(out.history.size()) < kMaxResidualHistory) out.history.emplace_back(out.iterations, r.linf, r.l2);
+    if (!std::isfinite(out.residual) || !std::isfinite(r.linf)) {
+      out.reason = "non-finite residual";
+      break;
+    }
+    if (out.residual <= tol) {
+      out.converged = true;
+      out.reason = std::string("converged: ") + name + " residual <= tol";
+      break;
+    }
+    if (out.iterations >= max_iters) {
+      out.reason = "max_iters reached";
+      break;
+    }
+    const int n = std::min(every, max_iters - out.iterations);
+    run(n);
+    out.iterations += n;
+  }
+  return out;
+}
+
+template <typename T>
 void StencilSolver<T>::synchronize() {
   // Direct halo: also wait for the neighbours' pushes into our tiles, so the
   // field (ghost ring included) is final and no peer still writes into it.

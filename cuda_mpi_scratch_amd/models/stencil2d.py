@@ -384,6 +384,84 @@ class Stencil2D:
             ops.stencil5(self._cur, self._nxt, g, 0, g.height, cfg.c_center, cfg.c_neighbor)
         self._cur, self._nxt = self._nxt, self._cur
 
+    # ---------------------------------------------------------- convergence
+    MAX_RESIDUAL_HISTORY = 4096  # checks kept in run_until()'s history (StencilSolver: kMaxResidualHistory)
+    # run_until's default chunk in time blocks (StencilSolver: kDefaultCheckBlocks; measured, docs/PERF.md).
+    DEFAULT_CHECK_BLOCKS = 16
+
+    def residual(self) -> dict:
+        """Collective (jacobi5): the norms of the Jacobi residual ``r = A u - u``
+        over the global core — exactly the change the next single step would
+        make — agreed over ranks: ``{"linf": max |r|, "l2": sqrt(sum r^2),
+        "cells": global cells}``. It needs the current field and a fresh 1-deep
+        ghost ring only (beside a fixed edge the ring holds the boundary
+        values), and leaves the field unchanged. The native solver runs the HIP
+        kernel ``ops.stencil5_residual``; the torch backend exchanges through
+        ``TorchHalo`` and evaluates the reference expression."""
+        if self.cfg.kind != "jacobi5":
+            raise ValueError("residual: only the 5-point Jacobi stencil has a residual (kind is 'box')")
+        if self.solver is not None:
+            r = self.solver.residual()
+            return {"linf": float(r["linf"]), "l2": float(r["l2"]), "cells": int(r["cells"])}
+        g = self.geom
+        self.halo.exchange(self._cur)
+        if self.device.type == "cuda":
+            torch.cuda.synchronize()
+        v = self._cur.view(g.total_height(), g.pitch)[:, g.x_origin:g.x_origin + g.total_width()]
+        linf, l2 = ops.residual5_reference(v, (g.halo_y, g.halo_x), self.cfg.c_center, self.cfg.c_neighbor)
+        # A NaN travels as +inf (a max of NaNs depends on the order); the squares
+        # are summed in rank order, so every rank gets the same bits.
+        linf = self.ctx.allreduce_max(linf if math.isfinite(linf) else math.inf)
+        sumsq = sum(self.ctx.gather_floats(l2 * l2)) if self.ctx.is_distributed else l2 * l2
+        return {"linf": linf, "l2": math.sqrt(sumsq) if sumsq >= 0 else math.nan, "cells": self.cells_per_step}
+
+    def run_until(self, tol: float, max_iters: int, check_every: int = 0, norm: str = "linf") -> dict:
+        """Collective: iterate until converged. Checks the residual first (an
+        already converged field returns after 0 iterations), then repeats
+        ``run(min(check_every, remaining))`` + ``residual()`` until the agreed
+        norm (``"linf"`` or ``"l2"``) is <= ``tol``, ``max_iters`` iterations
+        ran, or the norm is not finite (stops at once). ``check_every=0``:
+        ``DEFAULT_CHECK_BLOCKS`` (16) x the time block. Every rank stops at the same iteration. Returns
+        ``{"converged", "iterations", "residual", "checks", "reason", "norm",
+        "history": [(iteration, linf, l2), ...]}``; ``self.iteration`` advances
+        by the iterations actually run."""
+        if self.cfg.kind != "jacobi5":
+            raise ValueError("run_until: only the 5-point Jacobi stencil has a residual (kind is 'box')")
+        if norm not in ("linf", "l2"):
+            raise ValueError(f"run_until: norm must be 'linf' or 'l2', got {norm!r}")
+        if not tol >= 0:
+            raise ValueError(f"run_until: tol must be >= 0, got {tol}")
+        if max_iters < 0 or check_every < 0:
+            raise ValueError(f"run_until: max_iters and check_every must be >= 0, got {max_iters}, {check_every}")
+        if self.solver is not None:
+            out = dict(self.solver.run_until(float(tol), int(max_iters), int(check_every), norm))
+            out["history"] = [tuple(h) for h in out["history"]]
+            self.iteration += out["iterations"]
+            return out
+        every = check_every if check_every > 0 else self.DEFAULT_CHECK_BLOCKS * self.time_block
+        out = {"converged": False, "iterations": 0, "residual": 0.0, "checks": 0, "reason": "", "norm": norm,
+               "history": []}
+        while True:
+            r = self.residual()
+            out["checks"] += 1
+            out["residual"] = r[norm]
+            if len(out["history"]) < self.MAX_RESIDUAL_HISTORY:
+                out["history"].append((out["iterations"], r["linf"], r["l2"]))
+            if not (math.isfinite(r[norm]) and math.isfinite(r["linf"])):
+                out["reason"] = "non-finite residual"
+                break
+            if r[norm] <= tol:
+                out["converged"] = True
+                out["reason"] = f"converged: {norm} residual <= tol"
+                break
+            if out["iterations"] >= max_iters:
+                out["reason"] = "max_iters reached"
+                break
+            n = min(every, max_iters - out["iterations"])
+            self.run(n)
+            out["iterations"] += n
+        return out
+
     def exchange(self):
         """One halo exchange of the current tile, no update (the reference's run)."""
         if self.solver is not None:
@@ -620,6 +698,13 @@ def main(argv=None) -> int:
     p.add_argument("--block-fixed-edges", action="store_true",
                    help="with --non-periodic: keep the time block (interior on the usual kernels, the frame along "
                         "the fixed edges on the held-side kernel) instead of one exchange per iteration")
+    p.add_argument("--tol", type=float, default=None,
+                   help="iterate until the residual norm is <= TOL (run_until) instead of --iters iterations; "
+                        "the timed region is the run_until")
+    p.add_argument("--max-iters", type=int, default=None, help="with --tol: the iteration cap (default: --iters)")
+    p.add_argument("--check-every", type=int, default=0,
+                   help="with --tol: iterations between residual checks (0 = 16 x the time block)")
+    p.add_argument("--norm", default="linf", choices=["linf", "l2"], help="with --tol: the norm compared with TOL")
     p.add_argument("--seed", type=int, default=StencilConfig.seed)
     p.add_argument("--checkpoint", default=None, help="write the final field to this grid file")
     p.add_argument("--resume", default=None, help="start from this grid file (any decomposition)")
@@ -644,21 +729,37 @@ def main(argv=None) -> int:
         if ctx.is_root:
             print(f"resumed from {args.resume} at iteration {hdr.iteration}", file=sys.stderr)
     st.run(args.warmup)
-    st.prepare(args.iters)
-    st.synchronize()
-    ctx.barrier()
-    t0 = time.perf_counter()
-    st.run(args.iters)
+    until = None
+    if args.tol is not None:
+        cap = args.iters if args.max_iters is None else args.max_iters
+        chunk = args.check_every if args.check_every > 0 else Stencil2D.DEFAULT_CHECK_BLOCKS * st.time_block
+        st.prepare(max(1, min(chunk, cap)))
+        st.synchronize()
+        ctx.barrier()
+        t0 = time.perf_counter()
+        until = st.run_until(args.tol, cap, args.check_every, args.norm)
+        iters = until["iterations"]
+    else:
+        st.prepare(args.iters)
+        st.synchronize()
+        ctx.barrier()
+        t0 = time.perf_counter()
+        st.run(args.iters)
+        iters = args.iters
     st.synchronize()
     ctx.barrier()
     dt = ctx.allreduce_max(time.perf_counter() - t0)
-    gcells = st.cells_per_step * args.iters / dt / 1e9
-    rec = {"metric": "stencil2d_gcells_per_s", "value": gcells, "ms_per_iter": dt / args.iters * 1e3,
+    gcells = st.cells_per_step * iters / dt / 1e9
+    rec = {"metric": "stencil2d_gcells_per_s", "value": gcells, "ms_per_iter": dt / max(iters, 1) * 1e3,
            "ranks": ctx.world_size, "dims": f"{rows}x{cols}", "config": asdict(cfg), "backend": st.backend,
            "graph": st.graph_status(), "iteration": st.iteration, "time_block": st.time_block,
            "fixed_edges": st.fixed_edge_note(), "halo_mode": st.halo_mode(),
            "evaluation": ("scaled form" if st.scaled_form_active else "sum form" if st.sum_form_active
                           else "per step")}
+    if until is not None:
+        rec.update(converged=until["converged"], iterations=until["iterations"], residual=until["residual"],
+                   checks=until["checks"], norm=until["norm"], reason=until["reason"], tol=args.tol,
+                   wall_s=dt)
     if args.checkpoint:
         st.save_checkpoint(args.checkpoint)
     if ctx.is_root:

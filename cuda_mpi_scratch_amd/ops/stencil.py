@@ -191,3 +191,54 @@ def jacobi_sum_reference_global(u: torch.Tensor, steps: int, c: float = 0.2) -> 
         v = (n + s) + h3
     c_t = float(torch.tensor(c, dtype=u.dtype))
     return v * torch.tensor(c_t ** steps, dtype=torch.float64).to(u.dtype)
+
+
+def stencil5_residual(src: torch.Tensor, geom, c_center: float = 0.2, c_neighbor: float = 0.2, stream=None):
+    """``(linf, sumsq)`` of the Jacobi residual ``r = A u - u`` over the core of a
+    ghost-ring tile: ``r = fma(c_neighbor, (n + s) + (w + e), c_center * v) - v``
+    per cell in the element type, ``linf = max |r|`` (NaN if any is),
+    ``sumsq = sum r^2`` in float64. GPU tensors run the HIP kernel
+    (``csrc/kernels/residual.hip``: one streaming read of the core and the ring
+    cells beside it, deterministic); CPU tensors the reference expression."""
+    if geom.halo_x < 1 or geom.halo_y < 1:
+        raise ValueError("stencil5_residual: the tile has no ghost ring (it needs one at least 1 deep)")
+    if src.is_cuda:
+        linf, sumsq = hip().stencil5_residual(src.data_ptr(), geom, c_center, c_neighbor, dtype_name(src),
+                                              _stream(stream))
+        return float(linf), float(sumsq)
+    v = src.view(geom.total_height(), geom.pitch)[:, geom.x_origin:geom.x_origin + geom.total_width()]
+    r = _residual_field(v, (geom.halo_y, geom.halo_x), c_center, c_neighbor)
+    return float(r.abs().max()) if r.numel() else 0.0, float((r * r).sum())
+
+
+def _residual_field(full: torch.Tensor, ring, c_center, c_neighbor) -> torch.Tensor:
+    """float64 residual of every core cell of a (total_height, total_width) view
+    whose ring is ``ring`` = (rows, columns) deep: the stencil value rounded to
+    the element type (jacobi_reference_global's arithmetic), minus the cell,
+    rounded to the element type again."""
+    ry, rx = (ring, ring) if isinstance(ring, int) else ring
+    if ry < 1 or rx < 1:
+        raise ValueError("residual5_reference: the view has no ghost ring (it needs one at least 1 deep)")
+    H, W = full.shape[0] - 2 * ry, full.shape[1] - 2 * rx
+    c = full[ry:ry + H, rx:rx + W]
+    n, s = full[ry - 1:ry - 1 + H, rx:rx + W], full[ry + 1:ry + 1 + H, rx:rx + W]
+    w, e = full[ry:ry + H, rx - 1:rx - 1 + W], full[ry:ry + H, rx + 1:rx + 1 + W]
+    sums = (n + s) + (w + e)
+    if full.dtype == torch.float32:
+        c1 = torch.tensor(c_neighbor, dtype=torch.float32).double()
+        prod = (torch.tensor(c_center, dtype=torch.float32) * c).double()
+        new = (c1 * sums.double() + prod).float()
+    else:
+        new = c_neighbor * sums + c_center * c
+    return (new - c).double()
+
+
+def residual5_reference(full: torch.Tensor, ring, c_center: float = 0.2, c_neighbor: float = 0.2):
+    """CPU reference of the residual norms on a ``(total_height, total_width)``
+    view (core + a ghost ring ``ring`` cells deep, an int or (rows, columns)):
+    ``(linf, l2)`` of ``A u - u`` over the core, reduced in float64. Only the
+    ring cells beside the core enter."""
+    r = _residual_field(full.detach().cpu(), ring, c_center, c_neighbor)
+    if r.numel() == 0:
+        return 0.0, 0.0
+    return float(r.abs().max()), float(torch.sqrt((r * r).sum()))
