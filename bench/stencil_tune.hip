@@ -128,7 +128,7 @@ void fillfit(const char* name, const float* in, float* out, const TileGeom& g, c
   const index_t groups = (g.width + OWG - 1) / OWG;
   for (index_t hh : heights) {
     PipeShares shares = PipeShares::equal((groups * hh + blocks - 1) / blocks);
-    pipe_starts(groups, hh, blocks, pipe_fill_rows<S0, S1, PF, LAG1>(), &shares);
+    pipe_starts(groups, hh, blocks, kernels::pipe_fill_rows(S0, S1, PF, LAG1), &shares);
     auto launch = [&](const float* I, float* O) {
       pipe_stamped<S0, S1, PF, false, LAG1><<<blocks, 2 * kBlock>>>(I, O, g.pitch, g.core_offset(), g.width, g.height,
                                                                      0, g.width, 0, hh, shares, c0, 0.2f, st.get());
@@ -184,7 +184,7 @@ void fillfit(const char* name, const float* in, float* out, const TileGeom& g, c
     std::printf("{\"fillfit\": \"%s\", \"W\": %ld, \"h\": %ld, \"groups\": %ld, \"rows_per_wg\": %.1f, "
                 "\"model_fill_rows\": %ld, \"wg_kcycles_median\": %.2f, \"wg_kcycles_max\": %.2f, \"span_us\": %.2f, "
                 "\"mhz\": %.0f, \"pass_kcycles\": %.1f}\n",
-                name, long(g.width), long(hh), long(groups), med(rows_mean), long(pipe_fill_rows<S0, S1, PF, LAG1>()),
+                name, long(g.width), long(hh), long(groups), med(rows_mean), long(kernels::pipe_fill_rows(S0, S1, PF, LAG1)),
                 med(med_c) / 1e3, med(max_c) / 1e3, med(span), med(mhz), med(span) * med(mhz) / 1e3);
     std::printf("{\"fillfit_skew\": \"%s\", \"h\": %ld, \"start_us_p50\": %.2f, \"start_us_max\": %.2f, "
                 "\"end_us_min\": %.2f, \"end_us_p50\": %.2f, \"end_us_max\": %.2f, \"xcd\": [",
@@ -357,7 +357,7 @@ Variant pipe(const float* in, float* out, const TileGeom& g, float* tmp = nullpt
       // permutes workgroups, so it keeps equal shares).
       PipeShares shares = PipeShares::equal(share);
       if (!XM && G == kWavesPerBlock && pipe_balanced() && blocks <= kMaxShareBlocks)
-        pipe_starts(groups, g.height, blocks, pipe_fill_rows<S0, S1, PF, LAG1>(), &shares);
+        pipe_starts(groups, g.height, blocks, kernels::pipe_fill_rows(S0, S1, PF, LAG1), &shares);
       stencil5_stream_pipe_kernel<S0, S1, PF, WRAP, PRIO, float, SUM, G, XM, JOINT, LAG1, XB><<<blocks, threads, 0, s>>>(
           I, O, g.pitch, g.core_offset(), g.width, g.height, 0, g.width, 0, g.height, shares, c0, 0.2f);
     };

@@ -72,7 +72,7 @@ std::function<void(const double*, double*, hipStream_t)> pipe_fn(const TileGeom&
     const index_t share = (groups * g.height + blocks - 1) / blocks;
     PipeShares shares = PipeShares::equal(share);
     if (pipe_balanced() && blocks <= kMaxShareBlocks)
-      pipe_starts(groups, g.height, blocks, pipe_fill_rows<S0, S1, PF, LAG1>(), &shares);
+      pipe_starts(groups, g.height, blocks, kernels::pipe_fill_rows(S0, S1, PF, LAG1), &shares);
     stencil5_stream_pipe_kernel<S0, S1, PF, WRAP, 0, double, SUM, 4, false, JOINT, LAG1, XB><<<blocks, 512, 0, s>>>(
         I, O, g.pitch, g.core_offset(), g.width, g.height, 0, g.width, 0, g.height, shares, c0, 0.2);
   };

@@ -21,6 +21,7 @@
 #include "mxs/grid/layout.hpp"
 #include "mxs/kernels/chunk_schedule.hpp"
 #include "mxs/kernels/fixed_edge_split.hpp"
+#include "mxs/kernels/pipe_form.hpp"
 
 namespace mxs {
 namespace kernels {
@@ -59,17 +60,17 @@ struct Stencil5Coeffs {
   // agreed absmax), or < 0: unknown. See fast_form_safe().
   double range = -1.0;
 };
-inline bool uses_sum_form(const Stencil5Coeffs& c) { return c.sum_form && c.center == c.neighbor; }
-// The scaled form (stencil_device.hpp): unequal coefficients, c_neighbor != 0,
-// in the fp32 pipeline (20 / 24) and balanced stream kernel (2-16) and the fp64
-// wide pipeline (16); other depths and kernel forms run per step.
-inline bool uses_scaled_form(const Stencil5Coeffs& c) {
-  return c.sum_form && c.center != c.neighbor && c.neighbor != 0.0;
+// The fast form the coefficients ask for, before any bound (eval_form): the sum
+// form (equal coefficients) or the scaled form (unequal, c_neighbor != 0; it has
+// kernels in the fp32 pipeline (20 / 24) and balanced stream kernel (2-16) and
+// the fp64 wide pipeline (16); other depths and kernel forms run per step).
+inline EvalForm requested_form(const Stencil5Coeffs& c) {
+  if (!c.sum_form || c.neighbor == 0.0) return EvalForm::PerStep;
+  return c.center == c.neighbor ? EvalForm::Sum : EvalForm::Scaled;
 }
-// The kernel layer's guard of both fast forms for an S-level pass in element
-// type T (stencil5_tb and the chunk pass choose their form through it; the
-// solver's range guard is the measured, collective version of the same bounds,
-// and passes its bound in `range`):
+// The guard of both fast forms for an S-level pass in element type T, stated
+// once: stencil5_tb and the chunk pass choose their form through it, and the
+// solver calls it with its measured, agreed range:
 //   * |c_center| + 4 |c_neighbor| <= 1: the operator is bounded by the field;
 //   * c_neighbor^S is a normal number of T (it scales the stored result);
 //   * inside a pass the carried values grow by up to (4 + |k|)^S (k =
@@ -78,14 +79,35 @@ inline bool uses_scaled_form(const Stencil5Coeffs& c) {
 // sum form (|k| <= 1) is taken, under the sum form's documented contract
 // (max|u| 5^S < max/4 is the caller's); a faster-growing scaled form runs per
 // step (c_center 0.9, c_neighbor 0.013 grows as 73^S: 2e37 at S = 20).
+enum class FastFormVerdict : int {
+  Ok = 0,
+  NotFastPair,      // sum_form off, or c_neighbor == 0
+  Unbounded,        // |c_center| + 4 |c_neighbor| > 1
+  ScaleSubnormal,   // c_neighbor^S below the normal range of T
+  RangeOverflow,    // range (4 + |k|)^S >= max/4 (or the range is not finite)
+  RangeUnknownGrowth,  // range unknown and |k| > 1
+};
+template <typename T>
+inline FastFormVerdict fast_form_verdict(const Stencil5Coeffs& c, int S) {
+  if (requested_form(c) == EvalForm::PerStep) return FastFormVerdict::NotFastPair;
+  if (!(std::fabs(c.center) + 4.0 * std::fabs(c.neighbor) <= 1.0 + 1e-6)) return FastFormVerdict::Unbounded;
+  if (!(std::fabs(double(T(std::pow(c.neighbor, double(S))))) >= double(std::numeric_limits<T>::min())))
+    return FastFormVerdict::ScaleSubnormal;
+  const double k = std::fabs(c.center / c.neighbor);
+  if (c.range < 0.0) return k <= 1.0 ? FastFormVerdict::Ok : FastFormVerdict::RangeUnknownGrowth;
+  const bool fits =
+      std::isfinite(c.range) && c.range * std::pow(4.0 + k, double(S)) < double(std::numeric_limits<T>::max()) / 4.0;
+  return fits ? FastFormVerdict::Ok : FastFormVerdict::RangeOverflow;
+}
 template <typename T>
 inline bool fast_form_safe(const Stencil5Coeffs& c, int S) {
-  if (!(uses_sum_form(c) || uses_scaled_form(c))) return false;
-  if (!(std::fabs(c.center) + 4.0 * std::fabs(c.neighbor) <= 1.0 + 1e-6)) return false;
-  if (!(std::fabs(double(T(std::pow(c.neighbor, double(S))))) >= double(std::numeric_limits<T>::min()))) return false;
-  const double k = std::fabs(c.center / c.neighbor);
-  if (c.range < 0.0) return k <= 1.0;
-  return std::isfinite(c.range) && c.range * std::pow(4.0 + k, double(S)) < double(std::numeric_limits<T>::max()) / 4.0;
+  return fast_form_verdict<T>(c, S) == FastFormVerdict::Ok;
+}
+// The evaluation form of an S-level pass: the requested fast form inside its
+// bounds, else per step.
+template <typename T>
+inline EvalForm eval_form(const Stencil5Coeffs& c, int S) {
+  return fast_form_safe<T>(c, S) ? requested_form(c) : EvalForm::PerStep;
 }
 
 enum class StencilVariant : int {
@@ -134,6 +156,10 @@ constexpr index_t kMaxChunkBytes = 0x7F000000;
 // rows must be narrow enough that a piece holds at least this many (each piece
 // pays its own pipeline fill of S rows).
 constexpr index_t kMinChunkRows = 64;
+// Whether `rows` rows of `pitch` elements fit one descriptor-sized piece.
+constexpr bool chunk_rows_fit(index_t pitch, int elem_bytes, index_t rows = kMinChunkRows) {
+  return pitch * elem_bytes * rows <= kMaxChunkBytes;
+}
 // Measured default S for a w x h tile of `elem_bytes`-byte cells
 // (profiles/stencil_tuning/tunes_*, profiles/r02_deep/pipe*_*, profiles/r02_f64,
 // profiles/r02_sum): fp32 takes the two-stage pipeline at S = 20 (sum form,
@@ -148,10 +174,11 @@ inline int auto_time_block(index_t w, index_t h, int elem_bytes = 4, bool sum_fo
   // Rows too wide for kMinChunkRows per descriptor-sized piece (beyond ~8.3 M
   // fp32 columns; the padded pitch is at most w + 256): the fp32 pipelines
   // cannot take them, the single-wave kernels can (their non-descriptor body).
-  if (elem_bytes == 4 && (w + 256) * 4 * kMinChunkRows > kMaxChunkBytes) return kMaxTimeBlock;
+  if (elem_bytes == 4 && !chunk_rows_fit(w + 256, 4)) return kMaxTimeBlock;
   if (elem_bytes == 4 && w >= 1024 && h >= 1024) {
     // The pipeline runs workgroups of 4 strips; with joint stage-1 windows a
-    // group stores 912 columns at S = 20 (12 + 8) and 904 at S = 24 (12 + 12).
+    // group stores kOwgS20 = 912 columns at S = 20 (12 + 8) and kOwgS24 = 904
+    // at S = 24 (12 + 12).
     // A partial last group costs a whole one, except at S = 24 (ascending
     // order) when at most 440 columns are left for it: then it is split and
     // costs half (set_pipe_split). S = 24 when it needs no more groups than
@@ -164,7 +191,7 @@ inline int auto_time_block(index_t w, index_t h, int elem_bytes = 4, bool sum_fo
     // windows (profiles/pipe_split); the rule is kept as it is pinned by the
     // policy test, the 8192^2 rate floor and the config-2 cycle budget.
     auto groups = [&](int owg) { return (w + owg - 1) / owg; };
-    if (sum_form && groups(904) <= groups(912)) return 24;
+    if (sum_form && groups(kOwgS24) <= groups(kOwgS20)) return 24;
     // Tiles of >= 2^30 cells (chunks of ~4800 rows, warm-up negligible): the
     // deeper block relieves HBM and wins even at one group more, 32768^2 sum
     // form 11.1 T cells/s at S = 24 vs 10.9 at 20 (37 vs 36 groups). A 20-step
@@ -207,10 +234,8 @@ void stencil5_tb_held(const T* in, T* out, const TileGeom& g, int steps, index_t
 // workgroup-to-chunk assignment differs).
 struct ChunkPassShape {
   int steps = 0;
-  bool sum = false;   // sum form (c_center == c_neighbor and allowed)
-  bool scaled = false;  // scaled form (c_center != c_neighbor, c_neighbor != 0, allowed)
-  int js0 = 0;        // stage-0 levels of the joint windows
-  int lag1 = 0;       // level-order mask (stencil_pipe.hpp)
+  PipeForm form;      // joint windows: stage split and level order (pipe_form.hpp)
+  EvalForm eval = EvalForm::PerStep;
   int blocks = 0;     // resident workgroups (one per CU)
   index_t groups = 0;  // column groups of OWG output columns over the core width
   index_t owg = 0;
@@ -297,9 +322,9 @@ int gpu_share();
 // output). MXS_PIPE_JOINT=0 in the environment turns it off at start-up.
 void set_pipe_joint(bool on);
 bool pipe_joint();
-// Ascending level order (one row of lag per level) in the joint fp32 pipeline
-// where it measured faster: S = 20 on chunks of <= 768 rows (small and
-// multi-GPU tiles), S = 24 everywhere (stencil_pipe.hpp). Bitwise equal output.
+// Ascending level order (one row of lag per level) in the joint pipeline where
+// it measured faster: fp32 S = 20 and 24, fp64 S = 16 (pipe_form.hpp:
+// pipe_form_for). Bitwise equal output.
 // MXS_PIPE_LAG1=0 in the environment turns it off at start-up.
 void set_pipe_lag1(bool on);
 bool pipe_lag1();
@@ -317,6 +342,12 @@ bool pipe_split();
 // Whether the most recent stencil launch was a pipeline pass that split its
 // last group.
 bool last_pipe_split();
+// The three switches above as pipe_form_for() takes them.
+PipeSwitches pipe_switches();
+// The form of the most recent stencil launch if it was a pipeline pass (one
+// launch or chunk list), else PipeForm{}: one record with
+// last_stencil_dispatch(), last_pipe_lag1() and last_pipe_split().
+PipeForm last_pipe_form();
 // Fill-aware workgroup shares of the pipeline passes (chunk_schedule.hpp:
 // balanced_starts; default on): a share that crosses a column-group boundary
 // pays a second pipeline fill, and with equal row shares those workgroups set

@@ -37,8 +37,8 @@
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <limits>
 #include <cstdlib>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -57,13 +57,16 @@ constexpr int kLdsRows = 16;
 
 // Host-side record of the kernel form the last stencil launcher picked (the
 // tests assert that their shapes reach the kernel the benchmarks time).
-std::atomic<const char*> g_last_dispatch{"none"};
-std::atomic<bool> g_last_lag1{false};  // the pipeline launcher sets it after note()
-std::atomic<bool> g_last_split{false};  // likewise
-inline void note(const char* k) {
-  g_last_dispatch.store(k, std::memory_order_relaxed);
-  g_last_lag1.store(false, std::memory_order_relaxed);
-  g_last_split.store(false, std::memory_order_relaxed);
+struct LastLaunch {
+  const char* kernel = "none";
+  PipeForm form;       // pipeline passes only
+  bool split = false;  // the pass split its last group
+};
+std::mutex g_last_mutex;
+LastLaunch g_last;
+LastLaunch last_launch() {
+  std::lock_guard<std::mutex> lock(g_last_mutex);
+  return g_last;
 }
 
 // Tuned on MI355X with bench/stencil_tune.hip (profiles/stencil_tuning/*.log):
@@ -106,9 +109,9 @@ void stencil5_rows(const T* in, T* out, const TileGeom& g, index_t row_begin, in
     const size_t lds = size_t(kLdsRows + 2) * (kWaveSize * N + 2 * N) * sizeof(T);
     stencil5_lds_kernel<T, kLdsRows><<<dim3(unsigned(gx), unsigned(gy)), kBlock, lds, s>>>(
         in, out, g.pitch, g.core_offset(), g.width, row_begin, row_end, c0, c1);
-    note("lds");
+    note_launch("lds");
   } else {
-    note("roll");
+    note_launch("roll");
     if (g.width * int(sizeof(T)) >= 32768 * 4) launch_roll<T, 4>(in, out, g, row_begin, row_end, c0, c1, s);
     else launch_roll<T, 3>(in, out, g, row_begin, row_end, c0, c1, s);
   }
@@ -137,7 +140,7 @@ void stencil5_periodic(const T* in, T* out, const TileGeom& g, Stencil5Coeffs c,
   };
   if (g.width * int(sizeof(T)) >= 32768 * 4) go(std::integral_constant<int, 4>{});
   else go(std::integral_constant<int, 3>{});
-  note("roll_wrap");
+  note_launch("roll_wrap");
   MXS_HIP_CHECK_LAUNCH();
 }
 
@@ -149,12 +152,9 @@ void launch_tb_tile(const T* in, T* out, const TileGeom& g, index_t x0, index_t 
   const dim3 grid(unsigned((x1 - x0 + TW - 1) / TW), unsigned((y1 - y0 + TH - 1) / TH));
   stencil5_tb1_kernel<T, S, TW, TH, WRAP><<<grid, 256, lds, s>>>(in, out, g.pitch, g.core_offset(), g.width,
                                                                  g.height, x0, x1, y0, y1, c0, c1);
-  note("tb_tile");
+  note_launch("tb_tile");
 }
 
-// Workgroups of the balanced stream kernel resident at once on this device:
-// occupancy x CUs, at least 2 per CU (at S = 16, 1 fits; two rounds of
-// half-size shares still beat one round: profiles/stencil_tuning/tune16).
 // Rows in flight per wave (the fetch ring) of the fp32 rotated kernel: 6 up to
 // S = 12, where a 3-row lookahead (~1 us of work) no longer covers HBM latency
 // under load (8192^2, S = 12: +5%); 3 above, where 6 pushes S = 16 to 253
@@ -164,21 +164,16 @@ constexpr int stream_pf() {
   return (sizeof(T) == 4 && S <= 12) ? 6 : 3;
 }
 
+// Workgroups of the balanced stream kernel resident at once on this device:
+// at least 2 per CU (at S = 16, 1 fits; two rounds of half-size shares still
+// beat one round: profiles/stencil_tuning/tune16). Asked about the sum /
+// per-step rotated kernel (the scaled form shares its shape).
 template <typename T, int S, bool WRAP, bool SUM>
 int balanced_blocks() {
-  static int blocks = 0;
-  if (blocks == 0) {
-    int occ = 0, cus = 0, dev = 0;
-    MXS_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-        &occ,
-        reinterpret_cast<const void*>(
-            stencil5_stream_balanced_kernel<T, S, stream_pf<T, S>(), WRAP, true, sizeof(T) == 4, SUM>),
-        kBlock, 0));
-    MXS_HIP_CHECK(hipGetDevice(&dev));
-    MXS_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    blocks = std::max(occ, 2) * std::max(cus, 1);
-  }
-  return std::max(1, blocks / gpu_share());
+  return resident_workgroups(
+      reinterpret_cast<const void*>(
+          stencil5_stream_balanced_kernel<T, S, stream_pf<T, S>(), WRAP, true, sizeof(T) == 4, SUM>),
+      kBlock, 2);
 }
 
 // Wave-streaming kernels (stencil_device.hpp). Bulk rectangles: the balanced
@@ -195,17 +190,18 @@ int balanced_blocks() {
 // only kMinChunkRows rows have to fit).
 template <typename T>
 bool rot_ok(const TileGeom& g, index_t x1, index_t chunk_rows) {
-  return sizeof(T) == 4 && x1 % 4 == 0 && chunk_rows * g.pitch * index_t(sizeof(T)) <= kMaxChunkBytes;
+  return sizeof(T) == 4 && x1 % 4 == 0 && chunk_rows_fit(g.pitch, sizeof(T), chunk_rows);
 }
 
-// SUM: the balanced rotated kernel runs the sum form (sc = c^S, see
-// stencil_device.hpp), with XB = kScaledBody the scaled form (sc = c1^S,
-// k = c0 / c1); every other form keeps the per-step coefficients.
-template <typename T, int S, bool WRAP, bool SUM = false, int XB = 0>
+// EF: the balanced rotated kernel runs the fast forms (kernel_coeffs); every
+// other form keeps the per-step coefficients.
+template <typename T, int S, bool WRAP, EvalForm EF>
 void launch_stream(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1, T c0, T c1,
-                   T sc, hipStream_t s) {
+                   hipStream_t s) {
   constexpr int OW = StreamShape<T, S>::OW;
   constexpr bool kF32 = sizeof(T) == 4;
+  constexpr bool SUM = eval_sum(EF);
+  constexpr int XB = eval_xb(EF);
   const index_t strips = (x1 - x0 + OW - 1) / OW;
   const index_t rows = y1 - y0;
   const index_t groups = (strips + kWavesPerBlock - 1) / kWavesPerBlock;
@@ -213,14 +209,14 @@ void launch_stream(const T* in, T* out, const TileGeom& g, index_t x0, index_t x
   if (groups * rows >= index_t(blocks) * 64) {
     const index_t share = (groups * rows + blocks - 1) / blocks;
     if (kF32 && rot_ok<T>(g, x1, std::min<index_t>(kMinChunkRows, std::min(share, rows)))) {
-      const T kc = XB == kScaledBody ? T(double(c0) / double(c1)) : c1;
+      const KernelCoeffs<T> k = kernel_coeffs(EF, c0, c1, S);
       stencil5_stream_balanced_kernel<T, S, stream_pf<T, S>(), WRAP, true, kF32, SUM, XB><<<blocks, kBlock, 0, s>>>(
-          in, out, g.pitch, g.core_offset(), g.width, g.height, x0, x1, y0, y1, share, SUM ? sc : c0, kc);
-      note(XB == kScaledBody ? "stream_balanced_rot_scaled" : SUM ? "stream_balanced_rot_sum" : "stream_balanced_rot");
+          in, out, g.pitch, g.core_offset(), g.width, g.height, x0, x1, y0, y1, share, k.a, k.b);
+      note_launch(XB == kScaledBody ? "stream_balanced_rot_scaled" : SUM ? "stream_balanced_rot_sum" : "stream_balanced_rot");
     } else {
       stencil5_stream_balanced_kernel<T, S, 3, WRAP><<<blocks, kBlock, 0, s>>>(
           in, out, g.pitch, g.core_offset(), g.width, g.height, x0, x1, y0, y1, share, c0, c1);
-      note("stream_balanced");
+      note_launch("stream_balanced");
     }
     return;
   }
@@ -230,11 +226,11 @@ void launch_stream(const T* in, T* out, const TileGeom& g, index_t x0, index_t x
   if (kF32 && rot_ok<T>(g, x1, std::min(ch, rows))) {
     stencil5_stream_kernel<T, S, stream_pf<T, S>(), WRAP, true, kF32><<<grid, kBlock, 0, s>>>(
         in, out, g.pitch, g.core_offset(), g.width, g.height, x0, x1, y0, y1, ch, c0, c1);
-    note("stream_grid_rot");
+    note_launch("stream_grid_rot");
   } else {
     stencil5_stream_kernel<T, S, 3, WRAP><<<grid, kBlock, 0, s>>>(in, out, g.pitch, g.core_offset(), g.width,
                                                                   g.height, x0, x1, y0, y1, ch, c0, c1);
-    note("stream_grid");
+    note_launch("stream_grid");
   }
 }
 
@@ -244,12 +240,12 @@ void launch_stream(const T* in, T* out, const TileGeom& g, index_t x0, index_t x
 // boundary strips are only S rows or S columns thin; a bulk tile or a 256-column
 // wave strip would recompute 8-32x the strip, so thin strips get a matching thin
 // LDS tile (32 x 128 for column strips, 128 x 16 for row strips).
-// XB = kScaledBody (with SUM): the scaled form, on the fp64 wide pipeline at
-// S = 16 and the fp32 balanced stream kernel; the thin-strip tiles, the grid
-// form and the fp64 stream kernels run per step.
-template <typename T, int S, bool WRAP, bool SUM, int XB = 0>
+// EF: the fast forms run on the fp64 wide pipeline and the fp32 balanced stream
+// kernel; the thin-strip tiles, the grid form and the fp64 stream kernels run
+// per step.
+template <typename T, int S, bool WRAP, EvalForm EF>
 void launch_tb(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1, T c0, T c1,
-               T sc, StencilVariant v, hipStream_t s) {
+               StencilVariant v, hipStream_t s) {
   constexpr int TW = sizeof(T) == 4 ? 128 : 64;
   constexpr int NW = sizeof(T) == 4 ? 32 : 16;
   constexpr int NH = (sizeof(T) == 8 && S > 8) ? 64 : 128;  // keeps the fp64 thin tile under 64 KB of LDS
@@ -261,44 +257,35 @@ void launch_tb(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, i
     if (v == StencilVariant::LdsTile)
       return launch_tb_tile<T, S, TW, 32, WRAP>(in, out, g, x0, x1, y0, y1, c0, c1, s);
   }
-  if constexpr (sizeof(T) == 8 && S >= kPipeMinF64 && (XB == 0 || S == 16)) {
-    if (wide_pipe_ok<T, S, WRAP>(g, x0, x1, y0, y1))
-      return launch_pipe<T, S, WRAP, SUM, XB>(in, out, g, x0, x1, y0, y1, c0, c1, sc, s);
+  if constexpr (sizeof(T) == 8 && S >= kPipeMinF64) {
+    if (wide_pipe_ok<T, S, WRAP>(g, x0, x1)) return launch_pipe<T, S, WRAP, EF>(in, out, g, x0, x1, y0, y1, c0, c1, s);
   }
   // fp32: the balanced rotated kernel takes the sum or the scaled form; fp64's
   // stream kernels run per step.
-  launch_stream<T, S, WRAP, SUM && sizeof(T) == 4, sizeof(T) == 4 ? XB : 0>(in, out, g, x0, x1, y0, y1, c0, c1, sc, s);
+  launch_stream<T, S, WRAP, sizeof(T) == 4 ? EF : EvalForm::PerStep>(in, out, g, x0, x1, y0, y1, c0, c1, s);
 }
 
-// form: 1 = sum form (c_center == c_neighbor, allowed by the caller: the fast
-// bodies take sc = c^S), 2 = scaled form (c_center != c_neighbor: sc = c1^S and
-// k = c0 / c1; fp32 depths 2-16 and 20 / 24, fp64 16; elsewhere per step),
-// 0 = per step. S = 1 always keeps the per-step form.
+// form: the pass's evaluation form (kernels.hpp: eval_form). A scaled request
+// runs per step at depths without scaled kernels (pipe_form.hpp: scaled_depth),
+// and S = 1 always does.
 template <typename T, bool WRAP, int S = 1>
-void dispatch_tb(int steps, int form, const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0,
+void dispatch_tb(int steps, EvalForm form, const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0,
                  index_t y1, T c0, T c1, StencilVariant v, hipStream_t s) {
-  const T sc = T(std::pow(double(c1), double(S)));
-  if constexpr (S <= kMaxTimeBlock) {
-    if (steps == S) {
-      if constexpr (S > 1) {
-        if (form == 1) return launch_tb<T, S, WRAP, true>(in, out, g, x0, x1, y0, y1, c0, c1, sc, v, s);
-      }
-      if constexpr ((sizeof(T) == 8 && S == 16) || (sizeof(T) == 4 && S > 1)) {
-        if (form == 2)
-          return launch_tb<T, S, WRAP, true, kScaledBody>(in, out, g, x0, x1, y0, y1, c0, c1, sc, v, s);
-      }
-      return launch_tb<T, S, WRAP, false>(in, out, g, x0, x1, y0, y1, c0, c1, sc, v, s);
+  constexpr bool kDeep = S > kMaxTimeBlock;
+  if constexpr (S <= (sizeof(T) == 4 ? kMaxTimeBlockDeep : kMaxTimeBlock)) {
+    if (steps != S) return dispatch_tb<T, WRAP, S + 1>(steps, form, in, out, g, x0, x1, y0, y1, c0, c1, v, s);
+    auto go = [&](auto ef) {
+      constexpr EvalForm EF = decltype(ef)::value;
+      if constexpr (kDeep) launch_pipe<T, S, WRAP, EF>(in, out, g, x0, x1, y0, y1, c0, c1, s);
+      else launch_tb<T, S, WRAP, EF>(in, out, g, x0, x1, y0, y1, c0, c1, v, s);
+    };
+    if constexpr (S > 1) {
+      if (form == EvalForm::Sum) return go(std::integral_constant<EvalForm, EvalForm::Sum>{});
     }
-    return dispatch_tb<T, WRAP, S + 1>(steps, form, in, out, g, x0, x1, y0, y1, c0, c1, v, s);
-  } else if constexpr (S <= kMaxTimeBlockDeep && sizeof(T) == 4) {
-    if (steps == S) {
-      if (form == 1) return launch_pipe<T, S, WRAP, true>(in, out, g, x0, x1, y0, y1, c0, c1, sc, s);
-      if constexpr (S == 20 || S == 24) {
-        if (form == 2) return launch_pipe<T, S, WRAP, true, kScaledBody>(in, out, g, x0, x1, y0, y1, c0, c1, sc, s);
-      }
-      return launch_pipe<T, S, WRAP, false>(in, out, g, x0, x1, y0, y1, c0, c1, sc, s);
+    if constexpr (scaled_depth(int(sizeof(T)), S)) {
+      if (form == EvalForm::Scaled) return go(std::integral_constant<EvalForm, EvalForm::Scaled>{});
     }
-    return dispatch_tb<T, WRAP, S + 1>(steps, form, in, out, g, x0, x1, y0, y1, c0, c1, v, s);
+    go(std::integral_constant<EvalForm, EvalForm::PerStep>{});
   } else {
     MXS_CHECK(false, "stencil5_tb: steps must be in [1, " << (sizeof(T) == 4 ? kMaxTimeBlockDeep : kMaxTimeBlock)
                                                           << "], got " << steps);
@@ -328,10 +315,9 @@ void stencil5_tb(const T* in, T* out, const TileGeom& g, int steps, index_t x0, 
               "stencil5_tb: row padding too small for the x apron");
   }
   const T c0 = T(c.center), c1 = T(c.neighbor);
-  // Fast forms only inside their bounds (fast_form_safe: coefficients, c1^S
+  // Fast forms only inside their bounds (fast_form_verdict: coefficients, c1^S
   // normal, growth x the caller's range); else the per-step form.
-  const bool fast = v != StencilVariant::LdsTile && fast_form_safe<T>(c, steps);
-  const int form = !fast ? 0 : uses_sum_form(c) ? 1 : uses_scaled_form(c) ? 2 : 0;
+  const EvalForm form = v == StencilVariant::LdsTile ? EvalForm::PerStep : eval_form<T>(c, steps);
   if (wrap) dispatch_tb<T, true>(steps, form, in, out, g, x0, x1, y0, y1, c0, c1, v, s);
   else dispatch_tb<T, false>(steps, form, in, out, g, x0, x1, y0, y1, c0, c1, v, s);
   MXS_HIP_CHECK_LAUNCH();
@@ -347,7 +333,7 @@ void stencil5_rect(const T* in, T* out, const TileGeom& g, index_t x0, index_t x
   const index_t blocks = std::min<index_t>((n + kBlock - 1) / kBlock, index_t(device_cu_count()) * 8);
   stencil5_rect_kernel<T><<<unsigned(blocks), kBlock, 0, s>>>(in, out, g.pitch, g.core_offset(), x0, x1 - x0, y0,
                                                               y1 - y0, T(c.center), T(c.neighbor));
-  note("rect");
+  note_launch("rect");
   MXS_HIP_CHECK_LAUNCH();
 }
 
@@ -362,30 +348,26 @@ void stencil_box(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1,
     stencil_box_kernel<T, 1><<<grid, kBlock, 0, s>>>(in, out, g.pitch, g.core_offset(), x0, x1 - x0, y0, y1 - y0, w);
   else
     stencil_box_kernel<T, 2><<<grid, kBlock, 0, s>>>(in, out, g.pitch, g.core_offset(), x0, x1 - x0, y0, y1 - y0, w);
-  note("box");
+  note_launch("box");
   MXS_HIP_CHECK_LAUNCH();
 }
 
-const char* last_stencil_dispatch() { return g_last_dispatch.load(std::memory_order_relaxed); }
+const char* last_stencil_dispatch() { return last_launch().kernel; }
+PipeForm last_pipe_form() { return last_launch().form; }
+bool last_pipe_lag1() { return last_launch().form.lag1 != 0; }
+bool last_pipe_split() { return last_launch().split; }
 
 namespace {
 std::atomic<int> g_gpu_share{1};
-std::atomic<bool> g_pipe_joint{[] {
-  const char* e = experiment_env("MXS_PIPE_JOINT");  // experiments build only
+// The MXS_PIPE_* start-up switches (experiments build only): on unless "0".
+bool env_switch(const char* name) {
+  const char* e = experiment_env(name);
   return !(e && std::string(e) == "0");
-}()};
-std::atomic<bool> g_pipe_lag1{[] {
-  const char* e = experiment_env("MXS_PIPE_LAG1");  // experiments build only
-  return !(e && std::string(e) == "0");
-}()};
-std::atomic<bool> g_pipe_split{[] {
-  const char* e = experiment_env("MXS_PIPE_SPLIT");  // experiments build only
-  return !(e && std::string(e) == "0");
-}()};
-std::atomic<bool> g_pipe_balanced{[] {
-  const char* e = experiment_env("MXS_PIPE_BALANCED");  // experiments build only
-  return !(e && std::string(e) == "0");
-}()};
+}
+std::atomic<bool> g_pipe_joint{env_switch("MXS_PIPE_JOINT")};
+std::atomic<bool> g_pipe_lag1{env_switch("MXS_PIPE_LAG1")};
+std::atomic<bool> g_pipe_split{env_switch("MXS_PIPE_SPLIT")};
+std::atomic<bool> g_pipe_balanced{env_switch("MXS_PIPE_BALANCED")};
 }  // namespace
 void set_gpu_share(int processes) { g_gpu_share.store(std::max(1, processes), std::memory_order_relaxed); }
 int gpu_share() { return g_gpu_share.load(std::memory_order_relaxed); }
@@ -393,10 +375,9 @@ void set_pipe_joint(bool on) { g_pipe_joint.store(on, std::memory_order_relaxed)
 bool pipe_joint() { return g_pipe_joint.load(std::memory_order_relaxed); }
 void set_pipe_lag1(bool on) { g_pipe_lag1.store(on, std::memory_order_relaxed); }
 bool pipe_lag1() { return g_pipe_lag1.load(std::memory_order_relaxed); }
-bool last_pipe_lag1() { return g_last_lag1.load(std::memory_order_relaxed); }
 void set_pipe_split(bool on) { g_pipe_split.store(on, std::memory_order_relaxed); }
 bool pipe_split() { return g_pipe_split.load(std::memory_order_relaxed); }
-bool last_pipe_split() { return g_last_split.load(std::memory_order_relaxed); }
+PipeSwitches pipe_switches() { return {pipe_joint(), pipe_lag1(), pipe_split()}; }
 void set_pipe_balanced(bool on) { g_pipe_balanced.store(on, std::memory_order_relaxed); }
 bool pipe_balanced_on() { return g_pipe_balanced.load(std::memory_order_relaxed); }
 namespace detail {
@@ -420,9 +401,26 @@ void pipe_starts(index_t groups, index_t rows, int blocks, index_t fill, PipeSha
   out->n = blocks;
   for (int w = 0; w <= blocks; ++w) out->start[w] = int(hit->start[size_t(w)]);
 }
-void note_dispatch(const char* k) { note(k); }
-void note_pipe_lag1(bool lag1) { g_last_lag1.store(lag1, std::memory_order_relaxed); }
-void note_pipe_split(bool split) { g_last_split.store(split, std::memory_order_relaxed); }
+void note_launch(const char* kernel, const PipeForm& form, bool split) {
+  std::lock_guard<std::mutex> lock(g_last_mutex);
+  g_last = LastLaunch{kernel, form, split};
+}
+int resident_workgroups(const void* kernel, int threads, int min_per_cu) {
+  static std::mutex mutex;
+  static std::vector<std::pair<const void*, int>> memo;  // kernel -> workgroups per CU
+  int occ = 0;
+  {
+    std::lock_guard<std::mutex> lock(mutex);
+    for (const auto& e : memo)
+      if (e.first == kernel) occ = e.second;
+    if (occ == 0) {
+      MXS_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, 0));
+      occ = std::max(occ, 1);
+      memo.emplace_back(kernel, occ);
+    }
+  }
+  return std::max(1, std::max(occ, min_per_cu) * device_cu_count() / gpu_share());
+}
 }  // namespace detail
 
 #define MXS_INST_STENCIL(T)                                                                                    \

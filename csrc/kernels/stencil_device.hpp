@@ -265,16 +265,6 @@ __global__ __launch_bounds__(kBlock) void stencil_box_kernel(const T* __restrict
   }
 }
 
-// Tuned defaults (see docs/PERF.md for the sweep behind them).
-
-}  // namespace detail
-}  // namespace kernels
-}  // namespace mxs
-
-namespace mxs {
-namespace kernels {
-namespace detail {
-
 // LDS bytes of the ping-pong LDS tile (bench/tune_kernels.hpp: stencil5_tb_kernel,
 // the tuner's alternative); the single-buffer tile below takes half.
 template <typename T, int S, int TW, int TH>
@@ -283,14 +273,6 @@ constexpr size_t tb_lds_bytes() {
   constexpr int SA = ((S + N - 1) / N) * N;
   return size_t(2) * (TH + 2 * S) * (TW + 2 * SA + 2 * N) * sizeof(T);
 }
-
-}  // namespace detail
-}  // namespace kernels
-}  // namespace mxs
-
-namespace mxs {
-namespace kernels {
-namespace detail {
 
 // Single-LDS-buffer variant of stencil5_tb_kernel: each step reads its cells into
 // registers (a compile-time number of vectors per thread, statically indexed so
@@ -1156,34 +1138,7 @@ struct PipeShape {
   static constexpr int T1 = (3 * S0 + PF - 1 + PF - 1) / PF;  // stage-1 start block: ceil((3*S0 + PF - 1) / PF)
 };
 
-// Joint stage-1 windows (JOINT). In the layout above every strip pays the
-// apron of all S levels: 256 - 2 SA(S) output columns per strip (208 of 256 at
-// S = 24). Stage 1 does not need its own strip's stage-0 edges, though: the
-// level-S0 columns a stage-0 wave gets right (all but A0 = S0 rounded up to 4
-// per side) are laid side by side, for the G strips of the workgroup, in ONE
-// LDS row of G * OW0 valid columns, and stage 1's G windows (256 columns each,
-// stride OW1 = 256 - 2 A1) are cut from that row. Stage 0's apron is still
-// paid per strip, stage 1's once per group: OWG = G (256 - 2 A0) - 2 A1 output
-// columns per group, capped at G * OW1 (S = 24 as 12 + 12: 904 vs 4 x 208 =
-// 832, +8.7% per pass at the same VALU work; S = 20 as 8 + 12: 928 vs 864;
-// S = 28 as 12 + 16: 896 vs 800). The stage-0 lanes that hold no valid
-// column write into the row's tail (G * 2 A0 / 4 slots, exactly the lanes that
-// need one), which stage 1 only reads into columns it never stores. Same
-// operations per cell as the per-strip layout: bitwise identical output.
-template <int S0, int S1, int G>
-struct JointShape {
-  static constexpr int A0 = (S0 + 3) / 4 * 4, A1 = (S1 + 3) / 4 * 4;  // per-stage aprons (4-column lanes)
-  static constexpr int OW0 = 256 - 2 * A0;    // valid level-S0 columns per stage-0 wave
-  static constexpr int OW1 = 256 - 2 * A1;    // stride of stage 1's windows
-  static constexpr int SPAN = G * OW0;        // valid columns of the joint row
-  // Output columns per group: the joint row's valid span less stage 1's apron,
-  // or what the G windows can store (G * OW1) when that is less (A0 < A1).
-  static constexpr int OWG = SPAN - 2 * A1 < G * OW1 ? SPAN - 2 * A1 : G * OW1;
-  static constexpr int ROW = G * kWaveSize;   // joint row length in lane vectors (SPAN / 4 + the tail)
-  static constexpr int LEAD = A0 + A1;        // input columns left of the group's first output column
-  static_assert((G - 1) * OW1 + 256 <= 4 * ROW, "stage-1 windows must stay inside the joint row");
-  static_assert(OWG > 0, "time block too deep for a joint group");
-};
+// Joint stage-1 windows (JOINT): JointShape, mxs/kernels/pipe_form.hpp.
 
 // SUB (joint windows): the chunk may be one of several sub-groups of gs <= G
 // strips that share the workgroup and its barriers (the split narrow group of
@@ -1509,10 +1464,6 @@ __device__ __forceinline__ index_t wave_uniform(index_t v) {
   const unsigned long long u = static_cast<unsigned long long>(v);
   const unsigned lo = __builtin_amdgcn_readfirstlane(unsigned(u)), hi = __builtin_amdgcn_readfirstlane(unsigned(u >> 32));
   return index_t((static_cast<unsigned long long>(hi) << 32) | lo);
-}
-template <typename T, int S0, int S1, int G, bool JOINT, int LAG1>
-constexpr bool pipe_split_form() {
-  return JOINT && sizeof(T) == 4 && G == 4 && S0 == 12 && S1 == 12 && LAG1 == 3;
 }
 constexpr int kMaxShareBlocks = 512;
 struct PipeShares {

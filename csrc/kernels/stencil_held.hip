@@ -16,7 +16,7 @@
 namespace mxs {
 namespace kernels {
 namespace detail {
-void note_dispatch(const char* kernel);  // stencil.hip: last_stencil_dispatch() record
+void note_launch(const char* kernel, const PipeForm& form = {}, bool split = false);  // stencil.hip: the last-launch record
 }
 
 namespace {
@@ -81,7 +81,7 @@ void stencil5_tb_held(const T* in, T* out, const TileGeom& g, int steps, index_t
   MXS_CHECK(g.x_origin + g.halo_x >= sa && g.pitch >= g.x_origin + g.halo_x + ((g.width + N - 1) / N) * N + sa,
             "stencil5_tb_held: row padding too small for the x apron");
   dispatch_held<T>(steps, in, out, g, x0, x1, y0, y1, T(c.center), T(c.neighbor), hold, s);
-  note_dispatch("tb_held");
+  note_launch("tb_held");
   MXS_HIP_CHECK_LAUNCH();
 }
 

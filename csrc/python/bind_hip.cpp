@@ -306,8 +306,8 @@ PYBIND11_MODULE(_mxs_hip, m) {
           d["inner_blocks"] = hl.inner.blocks;
           d["outer_blocks"] = hl.outer.blocks;
           d["check"] = kernels::check_halo_last_schedule(hl, sh.groups, g.height, steps, ghost);
-          d["js0"] = sh.js0;
-          d["lag1"] = sh.lag1;
+          d["js0"] = sh.form.s0;
+          d["lag1"] = sh.form.lag1;
           d["fill"] = sh.fill;
           d["band"] = hl.band;
           d["inner_cost"] = hl.inner_cost;
@@ -326,6 +326,18 @@ PYBIND11_MODULE(_mxs_hip, m) {
       "of the pass the schedule assumes; part: both, inner or outer alone");
   m.def("last_pipe_lag1", &kernels::last_pipe_lag1,
         "whether the most recent stencil launch was a pipeline pass in ascending level order");
+  m.def(
+      "last_pipe_form",
+      [] {
+        const kernels::PipeForm f = kernels::last_pipe_form();
+        py::dict d;
+        d["js0"] = f.joint ? f.s0 : 0;
+        d["lag1"] = f.lag1;
+        d["split"] = kernels::last_pipe_split();
+        return d;
+      },
+      "the most recent stencil launch as a pipeline pass (one launch or chunk list): js0 (stage-0 levels of the "
+      "joint windows, 0: per-strip layout or no pipeline pass), lag1 (level-order mask), split (narrow last group)");
   m.def(
       "stencil5_tb_held",
       [](std::uintptr_t in, std::uintptr_t out, const TileGeom& g, int steps, index_t x0, index_t x1, index_t y0,

@@ -22,6 +22,20 @@ namespace {
 // Workgroups are dealt round-robin over the XCDs: both launches of an
 // interior-first pass are sized in multiples of this (kernels::make_halo_last_schedule).
 constexpr int kXcds = 8;
+
+// sum_form_note() for a verdict of the fast-form guard.
+const char* fast_form_note(kernels::FastFormVerdict v) {
+  switch (v) {
+    case kernels::FastFormVerdict::Unbounded:
+      return "fast form off: |c_center| + 4 |c_neighbor| > 1 (the S-level sums would not be bounded by the field)";
+    case kernels::FastFormVerdict::ScaleSubnormal:
+      return "fast form off: c_neighbor^S is below the normal range of the element type";
+    case kernels::FastFormVerdict::RangeOverflow:
+      return "fast form off: max|u| * (4 + |c_center / c_neighbor|)^S would overflow the element type (per-step form)";
+    default:
+      return "";
+  }
+}
 }  // namespace
 
 template <typename T>
@@ -185,24 +199,15 @@ StencilSolver<T>::StencilSolver(const CartTopology& topo, int rank, const TileGe
     opening_choice_ = "serial";
     opening_reason_ = "serial: fixed edges (the interior-first opening and the thin-strip overlap pass over held cells)";
   }
-  // Fast-form guard, coefficient part (the range part runs before the first
-  // pass): the sum form (c_center == c_neighbor) or the scaled form (unequal,
-  // c_neighbor != 0). Both carry v_l = u_l / c_neighbor^l through a pass, which
-  // grows by at most (4 + |c_center / c_neighbor|) per level, and need the
-  // operator bounded by the field (|c_center| + 4 |c_neighbor| <= 1) and
-  // c_neighbor^S in the normal range (it scales the stored result).
+  // Fast-form guard (kernels::fast_form_verdict), coefficient part: the range
+  // is unknown until ensure_range() measures it before the first pass.
   user_sum_ = cfg_.coeffs.sum_form;
-  const double cc = cfg_.coeffs.center, cn = cfg_.coeffs.neighbor;
-  if (user_sum_ && cfg_.kind == StencilKind::Jacobi5 && cn != 0.0) {
-    const T cs = T(std::pow(std::fabs(cn), double(block_)));
-    fast_growth_ = 4.0 + std::fabs(cc / cn);
-    if (!(std::fabs(cc) + 4.0 * std::fabs(cn) <= 1.0 + 1e-6)) {
-      sum_note_ = "fast form off: |c_center| + 4 |c_neighbor| > 1 (the S-level sums would not be bounded by the field)";
-    } else if (!(cs >= std::numeric_limits<T>::min())) {
-      sum_note_ = "fast form off: c_neighbor^S is below the normal range of the element type";
-    } else {
-      sum_coeffs_ok_ = true;
-    }
+  if (user_sum_ && cfg_.kind == StencilKind::Jacobi5) {
+    kernels::Stencil5Coeffs asked = cfg_.coeffs;
+    asked.range = -1.0;
+    const auto v = kernels::fast_form_verdict<T>(asked, block_);
+    sum_coeffs_ok_ = v == kernels::FastFormVerdict::Ok || v == kernels::FastFormVerdict::RangeUnknownGrowth;
+    sum_note_ = fast_form_note(v);
   }
   cfg_.coeffs.sum_form = user_sum_ && sum_coeffs_ok_;
 }
@@ -550,14 +555,16 @@ void StencilSolver<T>::ensure_range(bool collective) {
     range_agreed_ = true;
     agreed = true;
   }
-  const double bound = double(std::numeric_limits<T>::max()) / 4.0 / std::pow(fast_growth_, double(block_));
-  const bool ok = std::isfinite(md) && md < bound && (agreed || cfg_.coeffs.sum_form);
-  // The kernels re-check the same bound per pass (kernels::fast_form_safe):
-  // whenever `ok` holds here it holds there (S <= block_).
+  // The bound the kernels re-check per pass (kernels::fast_form_verdict), with
+  // the agreed range: whenever it holds here it holds there (S <= block_).
   cfg_.coeffs.range = md;
+  kernels::Stencil5Coeffs asked = cfg_.coeffs;
+  asked.sum_form = true;  // what the caller asked for; cfg_'s flag is the current verdict
+  const auto v = kernels::fast_form_verdict<T>(asked, block_);
+  const bool ok = v == kernels::FastFormVerdict::Ok && (agreed || cfg_.coeffs.sum_form);
   if (ok == cfg_.coeffs.sum_form) return;
   cfg_.coeffs.sum_form = ok;
-  sum_note_ = ok ? "" : "fast form off: max|u| * (4 + |c_center / c_neighbor|)^S would overflow the element type (per-step form)";
+  sum_note_ = fast_form_note(v);  // ok, or the range verdict: the coefficient part passed at construction
   // Captured graphs and chunk-pass shapes were built for the other form.
   wait_idle("sum-form switch");
   graphs_.clear();
@@ -677,9 +684,8 @@ std::unique_ptr<typename StencilSolver<T>::HaloLastPass> StencilSolver<T>::build
   } catch (const std::invalid_argument&) {
     return nullptr;
   }
-  // Chunks longer than kMaxChunkBytes run in pieces inside the kernel; rows
-  // must leave kMinChunkRows per piece.
-  if (tile_.pitch * index_t(sizeof(T)) * kernels::kMinChunkRows > kernels::kMaxChunkBytes) return nullptr;
+  // Chunks longer than kMaxChunkBytes run in pieces inside the kernel
+  // (chunk_pass_shape checked that rows leave kMinChunkRows per piece).
   hl->inner_shape = shape;
   hl->inner_shape.blocks = hl->sched.inner.blocks;
   hl->outer_shape = shape;

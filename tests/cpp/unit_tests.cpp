@@ -1,12 +1,14 @@
 // Host-only unit tests of the C++ core ("Unit tests"): region
 // algebra, accessor indexing, Cartesian neighbour tables, halo-plan
-// aggregation/ordering, the collective decision statistics and the
-// interior-first chunk schedule. Run by ctest and by tests/test_cpp_unit.py
-// (and under host ASan/UBSan by scripts/cpu_sanitize.sh).
+// aggregation/ordering, the collective decision statistics, the
+// interior-first chunk schedule, the pipeline form rule and the fast-form
+// guard. Run by ctest and by tests/test_cpp_unit.py (and under host ASan/UBSan
+// by scripts/cpu_sanitize.sh).
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
 #include <vector>
 #include <set>
 #include <sstream>
@@ -17,6 +19,8 @@
 #include "mxs/grid/regions.hpp"
 #include "mxs/halo/plan.hpp"
 #include "mxs/kernels/chunk_schedule.hpp"
+#include "mxs/kernels/kernels.hpp"
+#include "mxs/kernels/pipe_form.hpp"
 #include "mxs/runtime/decision.hpp"
 #include "mxs/topo/cart.hpp"
 
@@ -182,7 +186,110 @@ static void test_halo_last_schedule() {
   EXPECT(mono);
 }
 
+// The pipeline form rule (kernels/pipe_form.hpp): the forms the measured rule
+// picks and the shape numbers that follow, as the kernels' constexpr shapes
+// gave them before the rule was stated once.
+static void test_pipe_form() {
+  using kernels::EvalForm;
+  using kernels::PipeForm;
+  using kernels::kLagBoth;
+  auto pick = [](int eb, int S, EvalForm e, index_t cols = 8192, kernels::PipeSwitches on = {}) {
+    return kernels::pipe_form_for(eb, S, e, cols, on);
+  };
+  auto is = [](const kernels::PipeChoice& c, int s0, int s1, int pf, bool joint, int lag1, EvalForm e) {
+    return c.form == PipeForm{s0, s1, pf, joint, lag1} && c.eval == e;
+  };
+  const kernels::PipeSwitches no_lag{true, false, true}, no_joint{false, true, true};
+  for (EvalForm e : {EvalForm::PerStep, EvalForm::Sum, EvalForm::Scaled}) {
+    EXPECT(is(pick(4, 20, e, 12284), 8, 12, 6, true, kLagBoth, e));
+    EXPECT(is(pick(4, 20, e, 12288), 12, 8, 6, true, kLagBoth, e));
+    EXPECT(is(pick(4, 20, e, 8192, no_lag), 12, 8, 6, true, 0, e));
+    EXPECT(is(pick(4, 20, e, 32768, no_lag), 12, 8, 6, true, 0, e));
+    EXPECT(is(pick(4, 24, e), 12, 12, 6, true, kLagBoth, e));
+    EXPECT(is(pick(4, 24, e, 8192, no_lag), 12, 12, 6, true, 0, e));
+    EXPECT(is(pick(8, 16, e), 8, 8, 3, true, kLagBoth, e));
+    EXPECT(is(pick(8, 16, e, 8192, no_lag), 8, 8, 3, true, 0, e));
+  }
+  EXPECT(is(pick(4, 20, EvalForm::Sum, 8192, no_joint), 10, 10, 6, false, 0, EvalForm::Sum));
+  EXPECT(is(pick(4, 20, EvalForm::PerStep, 8192, no_joint), 11, 9, 6, false, 0, EvalForm::PerStep));
+  EXPECT(is(pick(4, 20, EvalForm::Scaled, 8192, no_joint), 11, 9, 6, false, 0, EvalForm::PerStep));
+  EXPECT(is(pick(8, 16, EvalForm::Scaled, 8192, no_joint), 8, 8, 3, false, 0, EvalForm::PerStep));
+  for (EvalForm e : {EvalForm::PerStep, EvalForm::Sum}) {
+    EXPECT(is(pick(4, 28, e), 12, 16, 6, true, 0, e));
+    EXPECT(is(pick(4, 32, e), 16, 16, 3, true, 0, e));
+    EXPECT(is(pick(8, 12, e), 6, 6, 3, false, 0, e));
+    EXPECT(is(pick(8, 9, e), 4, 5, 3, false, 0, e));
+  }
+  EXPECT(is(pick(4, 28, EvalForm::Scaled), 12, 16, 6, true, 0, EvalForm::PerStep));  // no scaled kernels at 28
+  EXPECT(is(pick(4, 17, EvalForm::PerStep), 9, 8, 6, false, 0, EvalForm::PerStep));
+  EXPECT(is(pick(4, 17, EvalForm::Sum), 8, 9, 6, false, 0, EvalForm::Sum));
+  EXPECT(is(pick(4, 31, EvalForm::PerStep), 16, 15, 3, false, 0, EvalForm::PerStep));
+  EXPECT(is(pick(4, 29, EvalForm::PerStep), 15, 14, 3, false, 0, EvalForm::PerStep));
+  // Only the fp32 12 + 12 ascending form splits its narrow last group.
+  EXPECT(pick(4, 24, EvalForm::Sum).split && !pick(4, 24, EvalForm::Sum, 8192, no_lag).split);
+  EXPECT(!pick(4, 24, EvalForm::Sum, 8192, kernels::PipeSwitches{true, true, false}).split);
+  EXPECT(!pick(4, 20, EvalForm::Sum, 32768).split && !pick(8, 16, EvalForm::Sum).split);
+
+  // Output columns per group.
+  auto owg = [](int s0, int s1) { return kernels::pipe_owg(PipeForm{s0, s1, 6, true, 0}); };
+  EXPECT(owg(12, 8) == 912 && owg(12, 12) == 904 && owg(8, 12) == 928);
+  EXPECT(owg(12, 16) == 896 && owg(16, 16) == 864 && owg(8, 8) == 944);
+  EXPECT(kernels::pipe_owg(PipeForm{10, 10, 6, false, 0}) == 4 * 216);  // per strip: 256 - 2 * 20
+  EXPECT(kernels::pipe_owg(PipeForm{9, 8, 6, false, 0}) == 4 * 216);    // S = 17: the apron rounds up to 20
+  EXPECT(kernels::pipe_owg(PipeForm{6, 6, 3, false, 0}) == 4 * 232);
+  EXPECT(kernels::joint_owg(12, 12, 2) == 440);
+  EXPECT(kernels::pipe_groups(PipeForm{12, 12, 6, true, kLagBoth}, 32768) == 37);
+  EXPECT(kernels::pipe_groups(PipeForm{12, 8, 6, true, kLagBoth}, 32768) == 36);
+  // Read reach: lead A0 + A1, span 3 * OW0 + 256.
+  EXPECT(kernels::pipe_apron(PipeForm{12, 8, 6, true, 0}) == 20 && kernels::pipe_read_span(PipeForm{12, 8, 6, true, 0}) == 952);
+  EXPECT(kernels::pipe_apron(PipeForm{8, 12, 6, true, 0}) == 20 && kernels::pipe_read_span(PipeForm{8, 12, 6, true, 0}) == 976);
+  EXPECT(kernels::pipe_apron(PipeForm{12, 12, 6, true, 0}) == 24 && kernels::pipe_apron(PipeForm{8, 8, 3, true, 0}) == 16);
+  EXPECT(kernels::pipe_apron(PipeForm{9, 8, 6, false, 0}) == 20);
+  // Fill rows.
+  EXPECT(kernels::pipe_fill_rows(PipeForm{12, 8, 6, true, kLagBoth}) == 51);
+  EXPECT(kernels::pipe_fill_rows(PipeForm{8, 12, 6, true, kLagBoth}) == 53);
+  EXPECT(kernels::pipe_fill_rows(PipeForm{12, 12, 6, true, kLagBoth}) == 59);
+  // The split group: 32768 columns leave 224 for the 37th group of 904, 4096 leave 480.
+  const auto s24 = pick(4, 24, EvalForm::Sum);
+  EXPECT(kernels::pipe_split_half(s24, 32768, 4801) == 2401);
+  EXPECT(kernels::pipe_split_half(s24, 36 * 904 + 440, 100) == 50 && kernels::pipe_split_half(s24, 36 * 904 + 441, 100) == 0);
+  EXPECT(kernels::pipe_split_half(s24, 4096, 4096) == 0);
+  EXPECT(kernels::pipe_split_half(pick(4, 20, EvalForm::Sum, 32768), 32768 - 8, 4096) == 0);
+}
+
+// The fast-form guard (kernels.hpp: fast_form_verdict), one verdict per reason.
+static void test_fast_form_verdict() {
+  using V = kernels::FastFormVerdict;
+  using C = kernels::Stencil5Coeffs;
+  EXPECT(kernels::fast_form_verdict<float>(C{0.2, 0.2, true, -1.0}, 24) == V::Ok);
+  EXPECT(kernels::eval_form<float>(C{0.2, 0.2, true, -1.0}, 24) == kernels::EvalForm::Sum);
+  EXPECT(kernels::eval_form<double>(C{0.5, 0.125, true, 1.0}, 16) == kernels::EvalForm::Scaled);
+  EXPECT(kernels::fast_form_verdict<float>(C{0.2, 0.2, false, -1.0}, 24) == V::NotFastPair);
+  EXPECT(kernels::fast_form_verdict<float>(C{0.5, 0.0, true, -1.0}, 24) == V::NotFastPair);
+  EXPECT(kernels::fast_form_verdict<float>(C{0.9, 0.013, true, -1.0}, 20) == V::RangeUnknownGrowth);
+  EXPECT(kernels::eval_form<float>(C{0.9, 0.013, true, -1.0}, 20) == kernels::EvalForm::PerStep);
+  EXPECT(kernels::fast_form_verdict<float>(C{0.9, 0.013, true, 10.0}, 20) == V::RangeOverflow);  // 73^20 = 2e37
+  EXPECT(kernels::fast_form_verdict<float>(C{0.9, 0.013, true, 1.0}, 20) == V::Ok);
+  EXPECT(kernels::fast_form_verdict<float>(C{0.3, 0.2, true, 1.0}, 20) == V::Unbounded);
+  EXPECT(kernels::fast_form_verdict<float>(C{0.25, 0.25, true, 1.0}, 20) == V::Unbounded);
+  EXPECT(kernels::fast_form_verdict<float>(C{0.02, 0.02, true, 1.0}, 24) == V::ScaleSubnormal);  // 0.02^24 = 1.7e-41
+  EXPECT(kernels::fast_form_verdict<double>(C{0.02, 0.02, true, 1.0}, 24) == V::Ok);
+  for (int S : {16, 20, 24}) {
+    const double edge32 = double(std::numeric_limits<float>::max()) / 4.0 / std::pow(5.0, double(S));
+    EXPECT(kernels::fast_form_verdict<float>(C{0.2, 0.2, true, edge32 * (1.0 - 1e-9)}, S) == V::Ok);
+    EXPECT(kernels::fast_form_verdict<float>(C{0.2, 0.2, true, edge32 * (1.0 + 1e-9)}, S) == V::RangeOverflow);
+    const double edge64 = std::numeric_limits<double>::max() / 4.0 / std::pow(5.0, double(S));
+    EXPECT(kernels::fast_form_verdict<double>(C{0.2, 0.2, true, edge64 * (1.0 - 1e-9)}, S) == V::Ok);
+    EXPECT(kernels::fast_form_verdict<double>(C{0.2, 0.2, true, edge64 * (1.0 + 1e-9)}, S) == V::RangeOverflow);
+  }
+  EXPECT(kernels::fast_form_verdict<float>(C{0.2, 0.2, true, std::numeric_limits<double>::infinity()}, 20) ==
+         V::RangeOverflow);
+  EXPECT(kernels::fast_form_safe<float>(C{0.2, 0.2, true, 0.0}, 32));
+}
+
 int main() {
+  test_pipe_form();
+  test_fast_form_verdict();
   test_regions();
   test_layout();
   test_cart();
