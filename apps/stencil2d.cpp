@@ -333,9 +333,11 @@ int run(MpiEnv& env, const Cli& cli, const CartTopology& topo, const DeviceBindi
          << "\", \"time_block\": " << time_block << ", \"iters\": " << iters;
       if (solver) {
         js << ", \"interior_first_opening\": " << (solver->halo_last(solver->time_block()) ? "true" : "false");
-        if (!solver->opening_choice().empty()) js << ", \"opening_choice\": \"" << solver->opening_choice() << "\"";
+        if (solver->opening_record().choice != Choice::Undecided)
+          js << ", \"opening_choice\": \"" << to_string(solver->opening_record().choice) << "\"";
         js << ", \"last_opening\": \"" << solver->last_run_opening() << "\"";
-        if (!solver->steady_choice().empty()) js << ", \"steady_choice\": \"" << solver->steady_choice() << "\"";
+        if (solver->steady_choice() != Choice::Undecided)
+          js << ", \"steady_choice\": \"" << to_string(solver->steady_choice()) << "\"";
         if (!solver->direct_state().empty()) js << ", \"direct_halo\": \"" << solver->direct_state() << "\"";
         if (!solver->fixed_edge_note().empty()) js << ", \"fixed_edges\": \"" << solver->fixed_edge_note() << "\"";
       }

@@ -31,7 +31,7 @@
 // differs by its usual few ulp). Boundary values live in the ghost ring of
 // BOTH buffers (no exchange writes a physical side). The schedules that pass
 // over the full core another way are off on every rank: the thin-strip
-// overlap and the interior-first opening (opening_reason() says so).
+// overlap and the interior-first opening (opening_record().reason says so).
 //
 // Per super-step (cur -> nxt), serial (the default): the pass on the main
 // stream, then the exchange of its output (pack(nxt) -> RCCL -> unpack(nxt)):
@@ -79,10 +79,13 @@
 //
 // Collective invariants (every rank must issue the same RCCL groups in the same
 // order, whatever it decides locally):
-//   * every call with peers primes exactly once and issues one exchange per
-//     super-step but the bare last one; the interior-first opening IS the
-//     priming exchange, so a rank without a chunk-list form for its tile
-//     (uneven decomposition) runs prime + pass instead and stays in step;
+//   * run() executes a CallPlan (runtime/call_plan.hpp), which plan_call()
+//     computes from values that are the same on every rank and nothing
+//     rank-local: every call with peers primes exactly once and issues one
+//     exchange per super-step but the bare last one; the interior-first
+//     opening IS the priming exchange, so a rank without a chunk-list form for
+//     its tile (uneven decomposition) runs the plan's Opening step as exchange
+//     + pass instead and stays in step;
 //   * prepare()'s schedule decision is taken from timings agreed over ranks:
 //     each round times every opening from a device barrier on every rank, the
 //     ranks agree on the round's maximum of each (the window is the max over
@@ -121,6 +124,7 @@
 #include "mxs/halo/exchange.hpp"
 #include "mxs/halo/ipc_direct.hpp"
 #include "mxs/kernels/kernels.hpp"
+#include "mxs/runtime/call_plan.hpp"
 #include "mxs/runtime/decision.hpp"
 #include "mxs/runtime/hip_utils.hpp"
 
@@ -129,6 +133,42 @@ namespace mxs {
 enum class StencilKind : int { Jacobi5 = 0, Box = 1 };
 enum class Opening : int { Auto = 0, Serial = 1, InteriorFirst = 2 };
 enum class DirectHalo : int { Off = 0, On = 1, Validate = 2 };
+
+// A schedule decision (the opening's, the steady super-steps').
+enum class Choice : int { Undecided, Serial, InteriorFirst };
+inline const char* to_string(Choice c) {
+  return c == Choice::Serial ? "serial" : c == Choice::InteriorFirst ? "interior-first" : "";
+}
+// The direct halo's state; Validated and Rejected come with a detail text.
+enum class DirectState : int { None, On, Pending, Validated, Rejected };
+inline const char* to_string(DirectState s) {
+  switch (s) {
+    case DirectState::On: return "on";
+    case DirectState::Pending: return "pending validation";
+    case DirectState::Validated: return "validated";
+    case DirectState::Rejected: return "rejected";
+    default: return "";
+  }
+}
+
+// prepare()'s opening decision and the measurements it was taken from.
+struct OpeningRecord {
+  Choice choice = Choice::Undecided;
+  std::string reason;
+  // The decision's rule: "median" (a tie goes to interior-first) or "notch"
+  // (decision.hpp: opening_rule); "" before prepare() measured.
+  std::string rule;
+  // The statistics of the per-round maxima over ranks: baseline = the serial
+  // opening, candidate = the best interior-first outer set (all 0: not measured).
+  RoundDecision decision;
+  // The interior-first schedule's measured inputs (us, agreed max over ranks):
+  // the exchange's delay of the outer launch beside the inner one, the bare pass.
+  double lead_us = 0, pass_us = 0;
+  std::vector<std::vector<double>> lead_phases;  // this rank's (exchange end, inner end, outer end) per sample
+  // Paired ratios of the per-round maxima over ranks, per candidate (outer
+  // workgroups, ratio per round), and this rank's own per-round ratios.
+  std::vector<std::pair<int, std::vector<double>>> ratio_samples, local_ratio_samples;
+};
 
 // Event-timed phases of one untimed replica of a run's opening super-step
 // (StencilSolver::profile_window): what a short timed window spends where.
@@ -327,7 +367,7 @@ class StencilSolver {
   bool direct_halo() const { return direct_on_; }
   // The direct halo's state: "" (not configured), "on", "pending validation",
   // "validated: ..." or "rejected: ..." (with the measured reason).
-  const std::string& direct_state() const { return direct_state_; }
+  std::string direct_state() const { return to_string(direct_state_) + direct_detail_; }
   double direct_ms() const { return direct_ms_[1]; }
   double direct_backend_ms() const { return direct_ms_[0]; }
   // Fault injection for the validation: this rank corrupts one received ghost
@@ -345,41 +385,18 @@ class StencilSolver {
   // the following calls on one solver — Serial, InteriorFirst (needs the
   // form: interior-first allowed at construction) or Auto (back to the
   // opening construction / prepare() chose). Collective: every rank passes
-  // the same value. The decision's record (opening_choice()) is unchanged.
+  // the same value. The decision's record (opening_record()) is unchanged.
   void force_opening(Opening o);
   // The same for the later super-steps of a call (SolverConfig::steady).
   void force_steady(Opening o);
   // Whether the opening super-step of a call at depth S runs interior-first on
   // this rank (the opening is on and the tile has the chunk-list form).
   bool halo_last(int S) const;
-  // prepare()'s decision ("" before it decided, "serial" or "interior-first")
-  // and the statistics of the per-round maxima over ranks it was taken from.
-  const std::string& opening_choice() const { return opening_choice_; }
-  const std::string& opening_reason() const { return opening_reason_; }
-  // The decision's rule: "median" (a tie goes to interior-first) or "notch"
-  // (decision.hpp: opening_rule); "" before prepare() decided.
-  const std::string& opening_rule() const { return opening_rule_; }
-  // prepare()'s steady decision ("" before it decided, "serial" or
-  // "interior-first") and why.
-  const std::string& steady_choice() const { return steady_choice_; }
+  // prepare()'s opening decision (Undecided before it decided) with its measurements.
+  const OpeningRecord& opening_record() const { return opening_; }
+  // prepare()'s steady decision (Undecided before it decided) and why.
+  Choice steady_choice() const { return steady_choice_; }
   const std::string& steady_reason() const { return steady_reason_; }
-  double opening_serial_ms() const { return opening_ms_[0]; }
-  double opening_halo_last_ms() const { return opening_ms_[1]; }
-  double opening_serial_spread_ms() const { return opening_spread_[0]; }
-  double opening_ratio() const { return opening_ratio_; }
-  // The interior-first schedule's measured inputs (us, agreed max over ranks):
-  // the exchange's delay of the outer launch beside the inner one, the bare pass.
-  double opening_lead_us() const { return lead_us_; }
-  double opening_pass_us() const { return lead_pass_us_; }
-  const std::vector<std::vector<double>>& opening_lead_phases() const { return lead_phases_; }
-  double opening_ratio_iqr() const { return opening_spread_[1]; }
-  int opening_samples() const { return opening_samples_; }
-  // Paired ratios of the per-round maxima over ranks, per candidate (outer
-  // workgroups, ratio per round), and this rank's own per-round ratios.
-  const std::vector<std::pair<int, std::vector<double>>>& opening_ratio_samples() const { return opening_ratio_samples_; }
-  const std::vector<std::pair<int, std::vector<double>>>& opening_local_ratio_samples() const {
-    return opening_local_ratio_samples_;
-  }
 
   // How collective agreements travel: "host allgather", "rccl all-reduce" or
   // "none (one rank)". The device barrier before timed samples has its own
@@ -414,12 +431,16 @@ class StencilSolver {
   // Why the sum form is off when the coefficients are equal ("" when on).
   const std::string& sum_form_note() const { return sum_note_; }
   // (S, count) of the super-steps the last run() enqueued.
-  std::vector<std::pair<int, int>> last_run_blocks() const { return last_blocks_; }
+  std::vector<std::pair<int, int>> last_run_blocks() const {
+    std::vector<std::pair<int, int>> out;
+    for (int i = 0; i < last_plan_.n_blocks; ++i) out.emplace_back(last_plan_.blocks[i].S, last_plan_.blocks[i].count);
+    return out;
+  }
   // Halo exchanges the last run() enqueued (priming included).
-  int last_run_exchanges() const { return last_exchanges_; }
+  int last_run_exchanges() const { return last_plan_.exchanges; }
   // Opening of the last run(): "interior-first", "serial" (prime + pass),
-  // "fresh" (no priming exchange needed), "fused", "direct" or "" (no run).
-  const std::string& last_run_opening() const { return last_opening_; }
+  // "fresh" (no priming exchange needed), "fused", "direct", "overlap" or "" (no run).
+  std::string last_run_opening() const { return to_string(last_plan_.label, last_opening_form_); }
   int time_block() const { return block_; }
   // Fixed edges under time blocking: this rank's held sides and its split,
   // e.g. "held sides: top,left; interior 4056x1980 + 2 frame strips at S = 20"
@@ -469,16 +490,14 @@ class StencilSolver {
   GraphSet* graphs_for(int S, int count);
   bool capture(GraphSet& gs);
   int chain_for(int S) const;
-  // (size, count) groups of run(iters): ceil(iters / block_) near-equal blocks.
-  struct Group {
-    int S, count;
-  };
-  void split(int iters, Group out[2]) const;
-  // `count` super-steps of size S; `last_bare`: the last one is a pass without
-  // its trailing exchange (with peers, the next call primes anyway).
-  // `first`: the call's first group (an interior-first opening may take its
-  // first super-step).
-  void run_group(int S, int count, bool last_bare = false, bool first = false);
+  // The plan's Full step: `count` super-steps of size S with their exchange
+  // (graph chains, then the eager remainder).
+  void run_full(int S, int count);
+  // The plan run() last executed, and whether its primed opening found the
+  // chunk-list form on this rank.
+  CallPlan last_plan_;
+  bool last_opening_form_ = false;
+  SuperstepMode mode() const { return superstep_mode(fused_, direct_on_, cfg_.overlap); }
   void enqueue_bare_pass(T* cur, T* nxt, int S);  // post-exchange pass, no exchange after it
 
   // GPU markers of profile_window (nullptr in every other call).
@@ -506,9 +525,19 @@ class StencilSolver {
   // The exchange's delay of the outer launch as a share of the pass, measured
   // by choose_opening() on this run's real path (0: the model's estimate).
   double lead_frac_ = 0;
-  double lead_us_ = 0, lead_pass_us_ = 0;  // the agreed measurements behind it
-  std::vector<std::vector<double>> lead_phases_;  // this rank's (exchange end, inner end, outer end) per sample
   void enqueue_halo_last(T* cur, T* nxt, HaloLastPass* hl, Marks* marks = nullptr);
+  // The exchange of `tile` on `s`: one call, or pack / transfer / unpack with
+  // a mark behind each.
+  void exchange_marked(T* tile, hipStream_t s, Marks* marks);
+  // The serial opening, cur -> nxt: the exchange of cur's ring behind any side
+  // work, then the bare pass.
+  void serial_opening(T* cur, T* nxt, int S, Marks* marks = nullptr);
+  // cur_'s ring exchanged unless it is fresh.
+  void ensure_ring_fresh() {
+    if (ghost_fresh_) return;
+    prime_exchange();
+    ghost_fresh_ = true;
+  }
   // The priming exchange of a call's first super-step, interior-first where
   // this rank has the form, else exchange + pass: exactly one exchange either
   // way. Advances cur -> nxt when `advance`.
@@ -517,19 +546,10 @@ class StencilSolver {
   bool halo_last_on_ = false;                // a call's opening super-step runs interior-first
   std::vector<std::unique_ptr<HaloLastPass>> halo_lasts_;
   std::vector<int> no_halo_last_;
-  // Super-steps exchange AFTER their pass (the ghost ring of the next pass's
-  // input): every schedule but the fused periodic, the direct IPC halo and the
-  // thin-strip overlap, which exchange first.
-  bool post_exchange() const { return !fused_ && !direct_on_ && !cfg_.overlap; }
   // Sum-form range check: local measurement after a field change, agreed
   // over ranks at the first check and whenever `collective`.
   void ensure_range(bool collective);
   void begin_run(bool collective);           // range check + prime
-  double opening_ms_[2] = {0, 0};            // medians of the per-round maxima: prime + pass, interior-first (ms)
-  double opening_spread_[2] = {0, 0};        // IQRs: serial maxima (ms), paired ratio of maxima
-  double opening_ratio_ = 0;                 // median paired ratio of the maxima, interior-first / serial
-  int opening_samples_ = 0;
-  std::vector<std::pair<int, std::vector<double>>> opening_ratio_samples_, opening_local_ratio_samples_;
   // Host time (ms) from enqueue() to both streams drained: a timed window's
   // measure. No event goes on either stream (see choose_opening).
   template <typename F>
@@ -539,16 +559,27 @@ class StencilSolver {
     wait_idle(phase);
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - h0).count();
   }
-  std::string opening_choice_;               // "" before prepare() decided, "serial" or "interior-first"
-  std::string opening_reason_;
-  std::string opening_rule_;
+  // One bench-shaped timed sample: behind warm() (state-preserving launches of
+  // the sample's own path), from drained streams after a device barrier, the
+  // host clock from enqueue() to drained. Collective: one barrier.
+  template <typename W, typename F>
+  double timed_window(W&& warm, F&& enqueue, const char* phase) {
+    join_side();
+    warm();
+    join_side();
+    wait_idle(phase);
+    device_barrier(phase);
+    return host_span_ms(enqueue, phase);
+  }
+  OpeningRecord opening_;
   void choose_opening(int S);                // Opening::Auto: time both, agree, keep the faster
   void choose_steady(int S);                 // SolverConfig::steady Auto: the same for two super-steps
   RoundDecision paired_rounds(int rounds, const std::vector<std::function<double()>>& kinds,
                               const std::vector<bool>& have, const char* phase, std::vector<double>* local = nullptr,
                               WinRule rule = WinRule::Notch);
   bool steady_on_ = false;                   // every super-step interior-first (with the opening)
-  std::string steady_choice_, steady_reason_;
+  Choice steady_choice_ = Choice::Undecided;
+  std::string steady_reason_;
   bool side_pending_ = false;                // side-stream work not yet joined to main
   void join_side();                          // main stream waits for the side stream's work
   // Collective agreement: element-wise max over ranks (the host allgather when
@@ -569,8 +600,6 @@ class StencilSolver {
   void maybe_stall(const char* phase) const;
   int world_ = 1;                            // ranks of the topology
   bool ghost_fresh_ = false;                 // cur_'s ghost ring holds the neighbours' current bands
-  int last_exchanges_ = 0;
-  std::string last_opening_;
   bool multi_rank_ = false;                  // peers: every run call primes (begin_run)
   bool range_checked_ = false;              // local_absmax_ is this field's
   bool range_agreed_ = false;               // the ranks agreed on a range at least once
@@ -584,7 +613,6 @@ class StencilSolver {
   // use and kept (no hipFree before a timed window).
   DeviceBuffer<double> residual_buf_;
   DeviceBuffer<unsigned> residual_counter_;
-  std::vector<std::pair<int, int>> last_blocks_;
   std::string stall_phase_;
   double stall_s_ = 0;
 
@@ -602,7 +630,8 @@ class StencilSolver {
   std::unique_ptr<HaloExchanger<T>> ex_;
   std::unique_ptr<IpcDirectHalo<T>> direct_;  // SolverConfig::direct (On / Validate)
   bool direct_on_ = false;                    // super-steps use the direct push
-  std::string direct_state_;
+  DirectState direct_state_ = DirectState::None;
+  std::string direct_detail_;                 // what follows the state's name in direct_state()
   double direct_ms_[2] = {0, 0};              // agreed medians: backend opening, direct opening
   const RcclComm* barrier_comm_ = nullptr;   // set_barrier_comm (tests); default comm_
   std::string barrier_path_;

@@ -12,6 +12,7 @@
 #include "mxs/halo/plan.hpp"
 #include "mxs/kernels/chunk_schedule.hpp"
 #include "mxs/kernels/fixed_edge_split.hpp"
+#include "mxs/runtime/call_plan.hpp"
 #include "mxs/runtime/decision.hpp"
 #include "mxs/topo/cart.hpp"
 
@@ -216,6 +217,35 @@ PYBIND11_MODULE(_mxs_core, m) {
       "the lowest notch among candidates, which wins when its median ratio is <= 1 - min_gain (rule 'median', the "
       "opening) or its notch is below it (rule 'notch', the steady and direct-halo decisions) "
       "(runtime/decision.hpp); missing slots: kMissingSample");
+  m.def(
+      "plan_call",
+      [](int iters, int block, const std::string& mode, bool multi_rank, bool opening_on, bool steady_on,
+         bool ghost_fresh) {
+        MXS_CHECK(block >= 1, "plan_call: block must be >= 1");
+        const SuperstepMode md = mode == "fused"           ? SuperstepMode::Fused
+                                 : mode == "direct"        ? SuperstepMode::Direct
+                                 : mode == "overlap"       ? SuperstepMode::Overlap
+                                 : mode == "post-exchange" ? SuperstepMode::PostExchange
+                                                           : throw std::invalid_argument(
+                                                                 "mode must be fused, direct, overlap or post-exchange");
+        const CallPlan p = plan_call(iters, block, md, multi_rank, opening_on, steady_on, ghost_fresh);
+        static const char* const kinds[] = {"opening", "prime", "full", "bare"};
+        py::list steps, blocks;
+        for (int i = 0; i < p.n_steps; ++i)
+          steps.append(py::make_tuple(kinds[int(p.steps[i].kind)], p.steps[i].S, p.steps[i].count));
+        for (int i = 0; i < p.n_blocks; ++i) blocks.append(py::make_tuple(p.blocks[i].S, p.blocks[i].count));
+        py::dict d;
+        d["steps"] = steps;
+        d["blocks"] = blocks;
+        d["exchanges"] = p.exchanges;
+        // "primed": "interior-first" where the rank has the form at the first step's depth, else "serial".
+        d["label"] = p.label == OpeningLabel::Primed ? "primed" : to_string(p.label, false);
+        return d;
+      },
+      py::arg("iters"), py::arg("block"), py::arg("mode") = "post-exchange", py::arg("multi_rank") = false,
+      py::arg("opening_on") = false, py::arg("steady_on") = false, py::arg("ghost_fresh") = false,
+      "the steps of StencilSolver::run(iters) (runtime/call_plan.hpp): (kind, S, count) with kind opening | prime | "
+      "full | bare, the (S, count) blocks, the halo exchanges the call issues and its opening's label");
   m.attr("MISSING_SAMPLE") = kMissingSample;
   m.attr("HOLD_TOP") = unsigned(kernels::kHoldTop);
   m.attr("HOLD_BOTTOM") = unsigned(kernels::kHoldBottom);

@@ -60,6 +60,14 @@ kernels::StencilVariant parse_variant(const std::string& v) {
   throw std::invalid_argument("unknown stencil variant '" + v + "' (auto|roll|lds)");
 }
 
+// `what`: the argument's name (opening, steady).
+Opening parse_opening(const std::string& name, const char* what) {
+  if (name == "auto") return Opening::Auto;
+  if (name == "serial") return Opening::Serial;
+  if (name == "interior-first") return Opening::InteriorFirst;
+  throw std::invalid_argument(std::string(what) + " must be auto, serial or interior-first, got '" + name + "'");
+}
+
 kernels::DotReduce parse_reduce(const std::string& r) {
   if (r == "atomic") return kernels::DotReduce::Atomic;
   if (r == "two-pass" || r == "two_pass") return kernels::DotReduce::TwoPass;
@@ -550,10 +558,7 @@ PYBIND11_MODULE(_mxs_hip, m) {
                        bool block_fixed_edges) {
              SolverConfig cfg;
              cfg.block_fixed_edges = block_fixed_edges;
-             if (steady == "auto") cfg.steady = Opening::Auto;
-             else if (steady == "serial") cfg.steady = Opening::Serial;
-             else if (steady == "interior-first") cfg.steady = Opening::InteriorFirst;
-             else throw std::invalid_argument("steady must be auto, serial or interior-first, got '" + steady + "'");
+             cfg.steady = parse_opening(steady, "steady");
              if (direct_engine == "kernel") cfg.direct_engine = PushEngine::Kernel;
              else if (direct_engine == "copy-engine") cfg.direct_engine = PushEngine::CopyEngine;
              else throw std::invalid_argument("direct_engine must be kernel or copy-engine, got '" + direct_engine + "'");
@@ -561,10 +566,7 @@ PYBIND11_MODULE(_mxs_hip, m) {
              cfg.side_priority = side_priority;
              cfg.halo_max_ctas = halo_max_ctas;
              cfg.wire_delay_us = wire_delay_us;
-             if (opening == "auto") cfg.opening = Opening::Auto;
-             else if (opening == "serial") cfg.opening = Opening::Serial;
-             else if (opening == "interior-first") cfg.opening = Opening::InteriorFirst;
-             else throw std::invalid_argument("opening must be auto, serial or interior-first, got '" + opening + "'");
+             cfg.opening = parse_opening(opening, "opening");
              cfg.rehearse_peers = rehearse_peers;
              cfg.min_gain = min_gain;
              cfg.graph_max_superstep_us = graph_max_superstep_us;
@@ -613,10 +615,7 @@ PYBIND11_MODULE(_mxs_hip, m) {
       .def(
           "force_opening",
           [](SolverHandle& h, const std::string& o) {
-            const Opening op = o == "serial" ? Opening::Serial
-                               : o == "interior-first" ? Opening::InteriorFirst
-                               : o == "auto" ? Opening::Auto
-                                             : throw std::invalid_argument("opening: auto|serial|interior-first");
+            const Opening op = parse_opening(o, "opening");
             h.visit([op](auto& s) { s.force_opening(op); });
           },
           py::arg("opening"),
@@ -625,10 +624,7 @@ PYBIND11_MODULE(_mxs_hip, m) {
       .def(
           "force_steady",
           [](SolverHandle& h, const std::string& o) {
-            const Opening op = o == "serial" ? Opening::Serial
-                               : o == "interior-first" ? Opening::InteriorFirst
-                               : o == "auto" ? Opening::Auto
-                                             : throw std::invalid_argument("steady: auto|serial|interior-first");
+            const Opening op = parse_opening(o, "steady");
             h.visit([op](auto& s) { s.force_steady(op); });
           },
           py::arg("steady"), "paired measurements: the later super-steps' schedule of the following calls")
@@ -641,30 +637,31 @@ PYBIND11_MODULE(_mxs_hip, m) {
       .def("schedule_times",
            [](SolverHandle& h) {
              return h.visit([](auto& s) {
+               const OpeningRecord& o = s.opening_record();
                py::dict d;
-               d["opening"] = s.opening_choice();
-               d["reason"] = s.opening_reason();
-               d["rule"] = s.opening_rule();
-               d["serial_ms"] = s.opening_serial_ms();
-               d["interior_first_ms"] = s.opening_halo_last_ms();
-               d["serial_iqr_ms"] = s.opening_serial_spread_ms();
-               d["ratio"] = s.opening_ratio();
-               d["ratio_iqr"] = s.opening_ratio_iqr();
-               d["samples"] = s.opening_samples();
+               d["opening"] = to_string(o.choice);
+               d["reason"] = o.reason;
+               d["rule"] = o.rule;
+               d["serial_ms"] = o.decision.baseline_ms;
+               d["interior_first_ms"] = o.decision.candidate_ms;
+               d["serial_iqr_ms"] = o.decision.baseline_iqr;
+               d["ratio"] = o.decision.ratio;
+               d["ratio_iqr"] = o.decision.ratio_iqr;
+               d["samples"] = o.decision.rounds;
                d["outer_wgs"] = s.halo_last_outer_wgs(s.time_block());
                // Paired ratios of the per-round maxima over ranks per candidate
                // outer set, and this rank's own ratios (diagnostics).
                py::list rs, ls;
-               for (const auto& c : s.opening_ratio_samples()) rs.append(py::make_tuple(c.first, c.second));
-               for (const auto& c : s.opening_local_ratio_samples()) ls.append(py::make_tuple(c.first, c.second));
+               for (const auto& c : o.ratio_samples) rs.append(py::make_tuple(c.first, c.second));
+               for (const auto& c : o.local_ratio_samples) ls.append(py::make_tuple(c.first, c.second));
                d["candidate_ratios"] = rs;
                d["local_candidate_ratios"] = ls;
                d["agreement"] = s.agreement_path();
-               d["steady"] = s.steady_choice();
+               d["steady"] = to_string(s.steady_choice());
                d["steady_reason"] = s.steady_reason();
-               d["lead_us"] = s.opening_lead_us();
-               d["lead_pass_us"] = s.opening_pass_us();
-               d["lead_phases_us"] = s.opening_lead_phases();  // (exchange end, inner end, outer end)
+               d["lead_us"] = o.lead_us;
+               d["lead_pass_us"] = o.pass_us;
+               d["lead_phases_us"] = o.lead_phases;  // (exchange end, inner end, outer end)
                return d;
              });
            },

@@ -162,21 +162,18 @@ void StencilSolver<T>::device_barrier(const char* phase) {
 // paired ratios (decision.hpp): every rank adopts the same decision.
 template <typename T>
 void StencilSolver<T>::choose_opening(int S) {
-  if (!halo_last_allowed_ || cfg_.opening != Opening::Auto || !opening_choice_.empty()) return;
+  if (!halo_last_allowed_ || cfg_.opening != Opening::Auto || opening_.choice != Choice::Undecided) return;
   halo_last_on_ = true;
   HaloLastPass* hl = halo_last_pass(S, true);
   halo_last_on_ = false;
   std::vector<double> have{hl ? 1.0 : 0.0};
   agree_max(have, "prepare: opening agreement");
   if (have[0] == 0.0) {
-    opening_choice_ = "serial";
-    opening_reason_ = "no rank has an interior-first form at depth " + std::to_string(S);
+    opening_.choice = Choice::Serial;
+    opening_.reason = "no rank has an interior-first form at depth " + std::to_string(S);
     return;
   }
-  if (!ghost_fresh_) {
-    prime_exchange();
-    ghost_fresh_ = true;
-  }
+  ensure_ring_fresh();
   // The schedule's model needs the delay the exchange puts in front of the
   // outer launch (pack, wire, unpack beside the inner launch) as a share of the
   // pass. Both are measured here on the run's real path — an xGMI wire makes
@@ -199,12 +196,8 @@ void StencilSolver<T>::choose_opening(int S) {
       wait_idle("prepare: exchange lead");
       device_barrier("prepare: exchange lead");
       Marks marks;
-      if (hl) {
-        enqueue_halo_last(cur_, nxt_, hl, &marks);
-      } else {
-        prime_exchange();
-        core_pass(cur_, nxt_, S, main_.get());
-      }
+      if (hl) enqueue_halo_last(cur_, nxt_, hl, &marks);
+      else serial_opening(cur_, nxt_, S);
       wait_idle("prepare: exchange lead");
       if (rep == 0) continue;  // round 0 warms every shape
       pass.push_back(double(p1.since(p0)) * 1e3);
@@ -218,14 +211,14 @@ void StencilSolver<T>::choose_opening(int S) {
         if (marks.name[i] == "main:outer chunks") t_outer = t;
       }
       lead.push_back(t_unpack);
-      lead_phases_.push_back({t_unpack, t_inner, t_outer});
+      opening_.lead_phases.push_back({t_unpack, t_inner, t_outer});
     }
     std::vector<double> v{median_iqr(lead).first, median_iqr(pass).first};
     agree_max(v, "prepare: exchange lead");
-    lead_us_ = v[0];
-    lead_pass_us_ = v[1];
-    if (lead_us_ > 0 && lead_pass_us_ > 0) {
-      lead_frac_ = std::min(0.6, std::max(0.03, lead_us_ / lead_pass_us_));
+    opening_.lead_us = v[0];
+    opening_.pass_us = v[1];
+    if (opening_.lead_us > 0 && opening_.pass_us > 0) {
+      lead_frac_ = std::min(0.6, std::max(0.03, opening_.lead_us / opening_.pass_us));
       for (auto& h : halo_lasts_)
         if (h->S == S) {
           if (auto nh = build_halo_last(S, 0)) h = std::move(nh);
@@ -256,29 +249,15 @@ void StencilSolver<T>::choose_opening(int S) {
   // (profiles/r05_decision/decision_vs_window.txt), so the decision kept
   // serial where it should not have.
   auto timed = [&](auto&& enqueue) {
-    join_side();
-    enqueue_block(cur_, nxt_, S);
-    join_side();
-    wait_idle("prepare: opening timing");
-    device_barrier("prepare: opening timing");
-    return host_span_ms(enqueue, "prepare: opening timing");
+    return timed_window([&] { enqueue_block(cur_, nxt_, S); }, enqueue, "prepare: opening timing");
   };
   constexpr int nr = 20;  // paired rounds: the notch is 1.58 IQR / sqrt(20)
-  std::vector<std::function<double()>> kinds{[&] {
-    return timed([&] {
-      prime_exchange();
-      enqueue_bare_pass(cur_, nxt_, S);
-    });
-  }};
+  std::vector<std::function<double()>> kinds{[&] { return timed([&] { serial_opening(cur_, nxt_, S); }); }};
   for (int c = 0; c < kCands; ++c)
     kinds.emplace_back([&, c] {
       return timed([&] {
-        if (cands[c]) {
-          enqueue_halo_last(cur_, nxt_, cands[c]);
-        } else {
-          prime_exchange();
-          enqueue_bare_pass(cur_, nxt_, S);
-        }
+        if (cands[c]) enqueue_halo_last(cur_, nxt_, cands[c]);
+        else serial_opening(cur_, nxt_, S);
       });
     });
   std::vector<double> local;
@@ -286,33 +265,29 @@ void StencilSolver<T>::choose_opening(int S) {
   // pass (decision.hpp: opening_rule; the window sees the host's enqueue
   // latency in front of the serial opening's pass). The lead and the pass are
   // agreed values (max over ranks), so every rank takes the same rule.
-  const WinRule rule = mxs::opening_rule(lead_us_ > 0 && lead_pass_us_ > 0 ? lead_us_ / lead_pass_us_ : 0.0);
-  opening_rule_ = rule == WinRule::Median ? "median" : "notch";
-  const RoundDecision d = paired_rounds(nr, kinds, {true, !!cands[0], !!cands[1], !!cands[2]},
-                                        "prepare: opening agreement", &local, rule);
-  opening_local_ratio_samples_.clear();  // this rank's own paired ratios (diagnostics)
+  const WinRule rule =
+      mxs::opening_rule(opening_.lead_us > 0 && opening_.pass_us > 0 ? opening_.lead_us / opening_.pass_us : 0.0);
+  opening_.rule = rule == WinRule::Median ? "median" : "notch";
+  opening_.decision = paired_rounds(nr, kinds, {true, !!cands[0], !!cands[1], !!cands[2]},
+                                    "prepare: opening agreement", &local, rule);
+  const RoundDecision& d = opening_.decision;
+  opening_.local_ratio_samples.clear();  // this rank's own paired ratios (diagnostics)
   for (int c = 0; c < kCands; ++c) {
     if (!cands[c]) continue;
     std::vector<double> r(nr);
     for (int i = 0; i < nr; ++i) r[size_t(i)] = local[size_t((1 + c) * nr + i)] / std::max(local[size_t(i)], 1e-12);
-    opening_local_ratio_samples_.emplace_back(cands[c]->sched.outer.blocks, std::move(r));
+    opening_.local_ratio_samples.emplace_back(cands[c]->sched.outer.blocks, std::move(r));
   }
-  opening_ms_[0] = d.baseline_ms;
-  opening_ms_[1] = d.best >= 0 ? d.candidate_ms : 0.0;
-  opening_spread_[0] = d.baseline_iqr;
-  opening_spread_[1] = d.best >= 0 ? d.ratio_iqr : 0.0;
-  opening_ratio_ = d.best >= 0 ? d.ratio : 0.0;
-  opening_samples_ = nr;
-  opening_ratio_samples_.clear();
+  opening_.ratio_samples.clear();
   for (int c = 0; c < kCands; ++c)
     if (!d.ratios[size_t(c)].empty() && cands[c])
-      opening_ratio_samples_.emplace_back(cands[c]->sched.outer.blocks, d.ratios[size_t(c)]);
+      opening_.ratio_samples.emplace_back(cands[c]->sched.outer.blocks, d.ratios[size_t(c)]);
   if (d.win && d.best > 0 && alt[d.best]) {  // keep the measured best outer set for S
     for (auto& h : halo_lasts_)
       if (h->S == S) h = std::move(alt[d.best]);
   }
   halo_last_on_ = d.win;
-  opening_choice_ = d.win ? "interior-first" : "serial";
+  opening_.choice = d.win ? Choice::InteriorFirst : Choice::Serial;
   char buf[480];
   if (d.best < 0) {
     std::snprintf(buf, sizeof(buf), "no rank-wide interior-first candidate (serial median %.4f ms)", d.baseline_ms);
@@ -323,9 +298,9 @@ void StencilSolver<T>::choose_opening(int S) {
                   "%.4f / %.4f ms: %s; outer set %d workgroups from the measured exchange lead %.1f us of a %.1f us pass",
                   world_, nr, d.ratio, d.ratio_iqr, d.notch, rule == WinRule::Median ? "median" : "notch",
                   rule == WinRule::Median ? "<=" : "<", 1.0 - cfg_.min_gain, d.candidate_ms, d.baseline_ms,
-                  d.win ? "interior-first" : "serial kept", halo_last_outer_wgs(S), lead_us_, lead_pass_us_);
+                  d.win ? "interior-first" : "serial kept", halo_last_outer_wgs(S), opening_.lead_us, opening_.pass_us);
   }
-  opening_reason_ = buf;
+  opening_.reason = buf;
 }
 
 // The persistent snapshot scratch (ref_): n whole tiles (ghost rings included),
@@ -335,7 +310,7 @@ void StencilSolver<T>::choose_opening(int S) {
 template <typename T>
 T* StencilSolver<T>::scratch_tiles(int n) {
   const index_t elems = tile_.alloc_elems();
-  const int want = std::max(n, direct_ && direct_state_ == "pending validation" ? 2 : 1);
+  const int want = std::max(n, direct_ && direct_state_ == DirectState::Pending ? 2 : 1);
   if (ref_.size() >= index_t(n) * elems) return ref_.get();
   // try_reset: no error policy on a full device (an Abort policy would end the job).
   if (ref_.try_reset(index_t(want) * elems)) return ref_.get();
@@ -352,9 +327,10 @@ T* StencilSolver<T>::scratch_tiles(int n) {
 // samples advance the field (cur -> nxt -> cur): it is restored afterwards.
 template <typename T>
 void StencilSolver<T>::choose_steady(int S) {
-  if (cfg_.steady != Opening::Auto || !steady_choice_.empty() || !post_exchange()) return;
+  if (cfg_.steady != Opening::Auto || steady_choice_ != Choice::Undecided || mode() != SuperstepMode::PostExchange)
+    return;
   if (!halo_last_on_) {  // no interior-first opening: nothing to extend (config-level and agreed)
-    steady_choice_ = "serial";
+    steady_choice_ = Choice::Serial;
     steady_reason_ = "the opening is serial";
     return;
   }
@@ -372,38 +348,24 @@ void StencilSolver<T>::choose_steady(int S) {
   std::vector<double> no_room{snap ? 0.0 : 1.0};
   agree_max(no_room, "prepare: steady agreement");
   if (no_room[0] != 0.0) {
-    steady_choice_ = "serial";
+    steady_choice_ = Choice::Serial;
     steady_reason_ = "no room for the steady decision's field snapshot on some rank: serial kept";
     return;
   }
   MXS_HIP_CHECK(hipMemcpyAsync(snap, cur_, bytes, hipMemcpyDeviceToDevice, m));
   T* const a = cur_;
   T* const b = nxt_;
-  auto first = [&] {  // the call's interior-first opening, a -> b
-    if (hl) {
-      enqueue_halo_last(a, b, hl);
-    } else {
-      ex_->exchange(a, m);
-      core_pass(a, b, S, m);
-    }
-  };
   auto sample = [&](bool steady) {
     return [&, steady] {
-      join_side();
-      wait_idle("prepare: steady timing");
-      device_barrier("prepare: steady timing");
-      return host_span_ms(
-          [&] {
-            first();
-            if (steady && hl) {
-              enqueue_halo_last(b, a, hl);
-            } else {
-              join_side();
-              ex_->exchange(b, m);
-              core_pass(b, a, S, m);
-            }
-          },
-          "prepare: steady timing");
+      return timed_window([] {},
+                          [&] {
+                            // The call's interior-first opening, a -> b, then the second super-step, b -> a.
+                            if (hl) enqueue_halo_last(a, b, hl);
+                            else serial_opening(a, b, S);
+                            if (steady && hl) enqueue_halo_last(b, a, hl);
+                            else serial_opening(b, a, S);
+                          },
+                          "prepare: steady timing");
     };
   };
   constexpr int nr = 20;
@@ -413,7 +375,7 @@ void StencilSolver<T>::choose_steady(int S) {
   wait_idle("prepare: steady timing");
   ghost_fresh_ = false;
   steady_on_ = d.win;
-  steady_choice_ = d.win ? "interior-first" : "serial";
+  steady_choice_ = d.win ? Choice::InteriorFirst : Choice::Serial;
   char buf[320];
   std::snprintf(buf, sizeof(buf),
                 "two super-steps, the second interior-first / serial, paired ratio of the per-round maxima over %d "
@@ -471,7 +433,7 @@ void StencilSolver<T>::poison_ghost(T* tile) {
 // (2) wins. The current field is unchanged (restored, its ring re-exchanged).
 template <typename T>
 void StencilSolver<T>::validate_direct(int S) {
-  if (!direct_ || cfg_.direct != DirectHalo::Validate || direct_state_ != "pending validation") return;
+  if (!direct_ || cfg_.direct != DirectHalo::Validate || direct_state_ != DirectState::Pending) return;
   MXS_TRACE_RANGE("stencil.validate_direct");
   hipStream_t m = main_.get();
   join_side();
@@ -528,40 +490,26 @@ void StencilSolver<T>::validate_direct(int S) {
   ex_->exchange(cur_, m);  // the ring is the backend's again
   ghost_fresh_ = true;
   if (bad[0] != 0.0) {
-    direct_state_ = "rejected: the direct push differs from the " +
-                    std::string(cfg_.backend == HaloBackend::Rccl ? "RCCL" : "IPC") + " exchange in " +
-                    std::to_string(long(bad[0])) + " words on some rank over " + std::to_string(kSteps) +
-                    " super-steps";
+    direct_state_ = DirectState::Rejected;
+    direct_detail_ = ": the direct push differs from the " +
+                     std::string(cfg_.backend == HaloBackend::Rccl ? "RCCL" : "IPC") + " exchange in " +
+                     std::to_string(long(bad[0])) + " words on some rank over " + std::to_string(kSteps) +
+                     " super-steps";
     wait_idle("prepare: direct halo validation");
     return;
   }
   // Timing as choose_opening (host clock, no events), from drained streams
   // after a barrier, each sample behind a state-preserving pass of its own path.
-  auto timed = [&](auto&& warm, auto&& enqueue) {
-    join_side();
-    warm();
-    join_side();
-    wait_idle("prepare: direct halo timing");
-    device_barrier("prepare: direct halo timing");
-    return host_span_ms(enqueue, "prepare: direct halo timing");
-  };
+  auto timed = [&](auto&& warm, auto&& enqueue) { return timed_window(warm, enqueue, "prepare: direct halo timing"); };
   auto direct_opening = [&] {  // the priming push, the wait for the neighbours' pushes, the pass
     direct_->push(cur_, m);
     direct_->wait(m);
     update(cur_, nxt_, S, 0, w, 0, h, m);
   };
   constexpr int nr = 12;
-  auto backend = [&] {
-    return timed([&] { enqueue_block(cur_, nxt_, S); },
-                 [&] {
-                   if (halo_last_on_) {
-                     enqueue_opening(S, false);
-                   } else {
-                     prime_exchange();
-                     core_pass(cur_, nxt_, S, m);
-                   }
-                 });
-  };
+  // The backend's opening as run() enqueues it: interior-first where it is on
+  // and this rank has the form, else the serial one.
+  auto backend = [&] { return timed([&] { enqueue_block(cur_, nxt_, S); }, [&] { enqueue_opening(S, false); }); };
   const RoundDecision d = paired_rounds(nr, {backend, [&] { return timed(direct_opening, direct_opening); }},
                                         {true, true}, "prepare: direct halo timing");
   direct_ms_[0] = d.baseline_ms;
@@ -572,7 +520,8 @@ void StencilSolver<T>::validate_direct(int S) {
                 "%s, %d rounds: median %.3f, IQR %.3f, notch %.3f; medians %.4f / %.4f ms",
                 kSteps, cfg_.backend == HaloBackend::Rccl ? "RCCL" : "IPC", nr, d.ratio, d.ratio_iqr, d.notch,
                 d.candidate_ms, d.baseline_ms);
-  direct_state_ = std::string(d.win ? "validated: " : "rejected (slower): ") + buf;
+  direct_state_ = d.win ? DirectState::Validated : DirectState::Rejected;
+  direct_detail_ = std::string(d.win ? ": " : " (slower): ") + buf;
   // The timing pushes advanced the direct epochs and wrote the scratch
   // buffer's neighbours only; the current ring is the backend's (fresh).
   if (d.win) {
@@ -594,14 +543,16 @@ WindowPhases StencilSolver<T>::profile_window(int iters) {
   // agreed (the thin-strip overlap is a per-rank property).
   if (multi_rank_) ghost_fresh_ = false;
   ensure_range(true);
-  std::vector<double> skip{direct_on_ || (!fused_ && !post_exchange()) ? 1.0 : 0.0};
+  const SuperstepMode md = mode();
+  const bool fused = md == SuperstepMode::Fused;
+  std::vector<double> skip{md == SuperstepMode::Direct || md == SuperstepMode::Overlap ? 1.0 : 0.0};
   agree_max(skip, "profile_window");
   if (skip[0] != 0.0) {
     out.opening = direct_on_ ? "direct (not profiled)" : "overlap (not profiled)";
     return out;
   }
-  Group gr[2];
-  split(iters, gr);
+  BlockGroup gr[2];
+  split(iters, block_, gr);
   const int S = gr[0].count > 0 ? gr[0].S : gr[1].S;
   const int supersteps = gr[0].count + gr[1].count;
   hipStream_t m = main_.get();
@@ -611,39 +562,31 @@ WindowPhases StencilSolver<T>::profile_window(int iters) {
   Marks marks;
   const auto t0 = std::chrono::steady_clock::now();
   HaloLastPass* hl = nullptr;
-  if (!fused_ && halo_last_on_ && !ghost_fresh_) hl = halo_last_pass(S, true);
+  if (!fused && halo_last_on_ && !ghost_fresh_) hl = halo_last_pass(S, true);
   const bool primed = !ghost_fresh_;  // the replica's opening exchanges cur's ring
-  if (fused_) {  // the whole super-step is one wrap-around pass
+  // The window's first super-step has its own exchange unless it is the call's
+  // bare last one (peers): nxt is scratch, its ring is rewritten. Issued on
+  // every rank alike, whichever opening it ran.
+  const bool own_exchange = !(multi_rank_ && supersteps == 1);
+  if (fused) {  // the whole super-step is one wrap-around pass
     out.opening = "fused";
     marks.mark("main:start", m);
     enqueue_block(cur_, nxt_, S);
     marks.mark("main:pass", m);
   } else {
-    auto exchange = [&](T* tile) {
-      ex_->pack(tile, m);
-      marks.mark("main:pack", m);
-      ex_->transfer(m);
-      marks.mark("main:rccl", m);
-      ex_->unpack(tile, m);
-      marks.mark("main:unpack", m);
-      ++out.exchanges;
-    };
     if (hl) {
       out.opening = "interior-first";
       enqueue_halo_last(cur_, nxt_, hl, &marks);
-      ++out.exchanges;
       join_side();
     } else {
-      out.opening = ghost_fresh_ ? "fresh" : "serial";
+      out.opening = primed ? "serial" : "fresh";
       marks.mark("main:start", m);
-      if (!ghost_fresh_) exchange(cur_);
-      core_pass(cur_, nxt_, S, m);
+      if (primed) serial_opening(cur_, nxt_, S, &marks);
+      else core_pass(cur_, nxt_, S, m);
       marks.mark("main:pass", m);
     }
-    // The window's first super-step has its own exchange unless it is the
-    // call's bare last one (peers): nxt is scratch, its ring is rewritten.
-    // Issued on every rank alike, whichever opening it ran.
-    if (!(multi_rank_ && supersteps == 1)) exchange(nxt_);
+    if (own_exchange) exchange_marked(nxt_, m, &marks);
+    out.exchanges = (primed ? 1 : 0) + (own_exchange ? 1 : 0);
   }
   out.host_enqueue_us =
       std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
@@ -671,25 +614,20 @@ WindowPhases StencilSolver<T>::profile_window(int iters) {
   }
   // The unmarked replica: the same launches and exchanges on every rank, from
   // drained streams after a device barrier (cur -> nxt again, state unchanged).
-  join_side();
-  wait_idle("profile_window");
-  device_barrier("profile_window");
-  out.plain_wall_us = 1e3 * host_span_ms(
-                                [&] {
-                                  if (fused_) {
-                                    enqueue_block(cur_, nxt_, S);
-                                    return;
-                                  }
-                                  if (hl) {
-                                    enqueue_halo_last(cur_, nxt_, hl);
-                                    join_side();
-                                  } else {
-                                    if (primed) ex_->exchange(cur_, m);
-                                    core_pass(cur_, nxt_, S, m);
-                                  }
-                                  if (!(multi_rank_ && supersteps == 1)) ex_->exchange(nxt_, m);
-                                },
-                                "profile_window");
+  out.plain_wall_us = 1e3 * timed_window([] {},
+                                         [&] {
+                                           if (fused) return enqueue_block(cur_, nxt_, S);
+                                           if (hl) {
+                                             enqueue_halo_last(cur_, nxt_, hl);
+                                             join_side();
+                                           } else if (primed) {
+                                             serial_opening(cur_, nxt_, S);
+                                           } else {
+                                             core_pass(cur_, nxt_, S, m);
+                                           }
+                                           if (own_exchange) ex_->exchange(nxt_, m);
+                                         },
+                                         "profile_window");
   ghost_fresh_ = false;  // conservative: the next call re-primes
   return out;
 }

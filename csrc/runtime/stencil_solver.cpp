@@ -128,14 +128,14 @@ StencilSolver<T>::StencilSolver(const CartTopology& topo, int rank, const TileGe
     if (cfg_.direct == DirectHalo::On && cfg_.backend == HaloBackend::Ipc) {
       direct_ = std::make_unique<IpcDirectHalo<T>>(topo, rank, tile_, buf_a_, buf_b_, cfg_.bootstrap, boot.timeout_s);
       direct_on_ = true;
-      direct_state_ = "on";
+      direct_state_ = DirectState::On;
     } else if (cfg_.direct == DirectHalo::Validate && cfg_.backend != HaloBackend::Local) {
       MXS_CHECK(static_cast<bool>(cfg_.bootstrap), "direct halo validation needs a host allgather (bootstrap)");
       // Any devices: the validation in prepare() is the check the IPC
       // backend's cross-device refusal stands in for.
       direct_ = std::make_unique<IpcDirectHalo<T>>(topo, rank, tile_, buf_a_, buf_b_, cfg_.bootstrap, boot.timeout_s,
                                                    /*allow_cross_device=*/true);
-      direct_state_ = "pending validation";
+      direct_state_ = DirectState::Pending;
     }
   }
   if (direct_) direct_->set_engine(cfg_.direct_engine);
@@ -187,17 +187,17 @@ StencilSolver<T>::StencilSolver(const CartTopology& topo, int rank, const TileGe
   }
   halo_last_on_ = halo_last_allowed_ && cfg_.opening == Opening::InteriorFirst;
   steady_on_ = cfg_.steady == Opening::InteriorFirst;
-  if (cfg_.steady != Opening::Auto) steady_choice_ = steady_on_ ? "interior-first" : "serial";
+  if (cfg_.steady != Opening::Auto) steady_choice_ = steady_on_ ? Choice::InteriorFirst : Choice::Serial;
   if (halo_last_on_) {
-    opening_choice_ = "interior-first";
-    opening_reason_ = "forced (opening = interior-first)";
+    opening_.choice = Choice::InteriorFirst;
+    opening_.reason = "forced (opening = interior-first)";
   } else if (cfg_.opening == Opening::Serial) {
-    opening_choice_ = "serial";
-    opening_reason_ = "forced (opening = serial)";
+    opening_.choice = Choice::Serial;
+    opening_.reason = "forced (opening = serial)";
   }
   if (fixed_active_) {  // some rank holds a side: every rank runs the serial schedule
-    opening_choice_ = "serial";
-    opening_reason_ = "serial: fixed edges (the interior-first opening and the thin-strip overlap pass over held cells)";
+    opening_.choice = Choice::Serial;
+    opening_.reason = "serial: fixed edges (the interior-first opening and the thin-strip overlap pass over held cells)";
   }
   // Fast-form guard (kernels::fast_form_verdict), coefficient part: the range
   // is unknown until ensure_range() measures it before the first pass.
@@ -286,26 +286,27 @@ void StencilSolver<T>::enqueue_block(T* cur, T* nxt, int S) {
   MXS_TRACE_RANGE("stencil.superstep");
   const index_t h = tile_.height, w = tile_.width;
   hipStream_t m = main_.get(), side = side_.get();
-  if (fused_) {
-    if (S == 1) kernels::stencil5_periodic<T>(cur, nxt, tile_, cfg_.coeffs, m);
-    else kernels::stencil5_tb<T>(cur, nxt, tile_, S, 0, w, 0, h, cfg_.coeffs, true, m, cfg_.variant);
-    return;
-  }
-  if (direct_on_) {  // the neighbours pushed cur's ghost ring after their previous pass
-    direct_->wait(m);
-    core_pass(cur, nxt, S, m);
-    direct_->push(nxt, m);
-    return;
-  }
-  if (!cfg_.overlap) {
-    // Post-exchange: the pass first (cur's ghost ring is fresh, run_group
-    // sees to it), then the exchange of its output. The pass is on the GPU
-    // before the host has enqueued the RCCL group (~25 us of host time that
-    // a pre-exchange super-step leaves the GPU idle for).
-    core_pass(cur, nxt, S, m);
-    ex_->set_copy_block(0);  // alone on the GPU: the default (256-thread) copies
-    ex_->exchange(nxt, m);
-    return;
+  switch (mode()) {
+    case SuperstepMode::Fused:
+      if (S == 1) kernels::stencil5_periodic<T>(cur, nxt, tile_, cfg_.coeffs, m);
+      else kernels::stencil5_tb<T>(cur, nxt, tile_, S, 0, w, 0, h, cfg_.coeffs, true, m, cfg_.variant);
+      return;
+    case SuperstepMode::Direct:  // the neighbours pushed cur's ghost ring after their previous pass
+      direct_->wait(m);
+      core_pass(cur, nxt, S, m);
+      direct_->push(nxt, m);
+      return;
+    case SuperstepMode::PostExchange:
+      // The pass first (cur's ghost ring is fresh, the call's plan sees to
+      // it), then the exchange of its output. The pass is on the GPU before
+      // the host has enqueued the RCCL group (~25 us of host time that a
+      // pre-exchange super-step leaves the GPU idle for).
+      core_pass(cur, nxt, S, m);
+      ex_->set_copy_block(0);  // alone on the GPU: the default (256-thread) copies
+      ex_->exchange(nxt, m);
+      return;
+    case SuperstepMode::Overlap:
+      break;
   }
   // The thin-strip overlap: the exchange of cur under the interior.
   const index_t d = std::max(radius_, S);  // dependency depth of the super-step
@@ -429,78 +430,20 @@ typename StencilSolver<T>::GraphSet* StencilSolver<T>::graphs_for(int S, int cou
 }
 
 template <typename T>
-void StencilSolver<T>::split(int iters, Group out[2]) const {
-  out[0] = out[1] = Group{0, 0};
-  if (iters <= 0) return;
-  const int blocks = (iters + block_ - 1) / block_;
-  const int base = iters / blocks, extra = iters % blocks;  // extra blocks of base + 1
-  out[0] = Group{base + 1, extra};
-  out[1] = Group{base, blocks - extra};
-}
-
-template <typename T>
-void StencilSolver<T>::run_group(int S, int count, bool last_bare, bool first) {
-  if (count <= 0) return;
-  last_blocks_.emplace_back(S, count);
-  // Steady interior-first (SolverConfig::steady): every super-step exchanges
-  // its own input under the core chunks (the same exchanges in the same order
-  // as the serial schedule: one per super-step, the first the priming one).
-  if (steady_on_ && halo_last_on_ && post_exchange()) {
-    join_side();
-    if (first) last_opening_ = halo_last_pass(S, true) ? "interior-first" : "serial";
-    for (int i = 0; i < count; ++i) {
-      enqueue_opening(S, true);
-      ++last_exchanges_;
-    }
-    ghost_fresh_ = false;
-    return;
-  }
-  // The call's first super-step starts with a priming exchange (with peers:
-  // every call): interior-first when the opening is on (exactly one exchange
-  // whether or not this rank has the form, see enqueue_opening).
-  if (first && halo_last_on_ && post_exchange() && !ghost_fresh_) {
-    last_opening_ = halo_last_pass(S, true) ? "interior-first" : "serial";
-    enqueue_opening(S, true);
-    ++last_exchanges_;
-    ghost_fresh_ = false;  // its output's ring: primed by the next super-step / call
-    if (--count == 0) return;
-  }
-  join_side();  // an interior-first opening leaves side work pending
-  // Post-exchange super-steps: cur's ghost ring must be fresh before the first
-  // one; each leaves the next one's fresh. The thin-strip overlap schedule
-  // exchanges first and leaves it stale.
-  if (post_exchange() && !ghost_fresh_) {
-    if (first && last_opening_.empty()) last_opening_ = "serial";
-    prime_exchange();
-    ++last_exchanges_;
-  }
-  if (first && last_opening_.empty()) last_opening_ = post_exchange() ? "fresh" : "overlap";
-  // Direct halo: the call primed with a push (begin_run); the last pass's
-  // push would only feed the next call, which primes again: bare too.
-  last_bare = last_bare && (post_exchange() || direct_on_);
-  const int full = last_bare ? count - 1 : count;  // super-steps with their exchange
-  // Exchanges of the super-steps themselves (graph replays included): one each,
-  // the bare tail none; the fused periodic self-exchange is no exchange at all.
-  if (direct_on_) last_exchanges_ += full + (first ? 1 : 0);  // pushes, the priming one included
-  else if (!fused_) last_exchanges_ += post_exchange() ? full : count;
+void StencilSolver<T>::run_full(int S, int count) {
   int i = 0;
-  if (GraphSet* gs = full > 0 ? graphs_for(S, full) : nullptr) {
-    for (; i + gs->chain <= full; i += gs->chain) {
+  if (GraphSet* gs = graphs_for(S, count)) {
+    for (; i + gs->chain <= count; i += gs->chain) {
       MXS_TRACE_RANGE("stencil.graph_launch");
       const int k = cur_ == buf_a_ ? 0 : 1;
       gs->g[k].launch(main_.get());
       if (gs->chain % 2) std::swap(cur_, nxt_);  // an odd chain ends on the other buffer
     }
   }
-  for (; i < full; ++i) {  // no graph, or fewer than `chain` super-steps left
+  for (; i < count; ++i) {  // no graph, or fewer than `chain` super-steps left
     enqueue_block(cur_, nxt_, S);
     std::swap(cur_, nxt_);
   }
-  if (last_bare) {
-    enqueue_bare_pass(cur_, nxt_, S);
-    std::swap(cur_, nxt_);
-  }
-  ghost_fresh_ = post_exchange() && !last_bare;
 }
 
 // The last super-step of a call with peers: the pass alone, on the main stream.
@@ -519,7 +462,7 @@ void StencilSolver<T>::enqueue_bare_pass(T* cur, T* nxt, int S) {
 // current bands once; the first pass waits for the neighbours' pushes.
 template <typename T>
 void StencilSolver<T>::prime() {
-  if (direct_on_) direct_->push(cur_, main_.get());
+  if (mode() == SuperstepMode::Direct) direct_->push(cur_, main_.get());
 }
 
 template <typename T>
@@ -587,21 +530,38 @@ void StencilSolver<T>::begin_run(bool collective) {
 template <typename T>
 void StencilSolver<T>::run(int iters) {
   MXS_TRACE_RANGE("stencil.run");
-  last_blocks_.clear();
-  last_exchanges_ = 0;
+  last_plan_ = CallPlan{};
+  last_opening_form_ = false;
   last_forks_ = 0;
-  last_opening_.clear();
   if (iters <= 0) return;
   maybe_stall("run");
   begin_run(false);
-  if (fused_) last_opening_ = "fused";
-  if (direct_on_) last_opening_ = "direct";
-  Group gr[2];
-  split(iters, gr);
-  // With peers every call primes (begin_run), so the exchange after the call's
-  // last pass would be redundant: it ends on a bare pass (header).
-  const int last = gr[1].count > 0 ? 1 : 0, first = gr[0].count > 0 ? 0 : 1;
-  for (int k = 0; k < 2; ++k) run_group(gr[k].S, gr[k].count, multi_rank_ && k == last, k == first);
+  // What the call consists of is decided here, from nothing rank-local
+  // (call_plan.hpp); the steps below only enqueue it.
+  last_plan_ = plan_call(iters, block_, mode(), multi_rank_, halo_last_on_, steady_on_, ghost_fresh_);
+  const CallPlan& plan = last_plan_;
+  last_opening_form_ = plan.label == OpeningLabel::Primed && halo_last_pass(plan.steps[0].S, true) != nullptr;
+  for (int i = 0; i < plan.n_steps; ++i) {
+    const PlanStep& st = plan.steps[i];
+    switch (st.kind) {
+      case StepKind::Opening:
+        for (int c = 0; c < st.count; ++c) enqueue_opening(st.S, true);
+        break;
+      case StepKind::Prime:
+        exchange_only();  // behind the side work an interior-first opening leaves pending
+        break;
+      case StepKind::Full:
+        join_side();
+        run_full(st.S, st.count);
+        break;
+      case StepKind::Bare:
+        join_side();
+        enqueue_bare_pass(cur_, nxt_, st.S);
+        std::swap(cur_, nxt_);
+        break;
+    }
+  }
+  ghost_fresh_ = plan.ring_fresh;
 }
 
 template <typename T>
@@ -753,17 +713,8 @@ void StencilSolver<T>::enqueue_halo_last(T* cur, T* nxt, HaloLastPass* hl, Marks
   const int copy_wgs = halo_last_copy_wgs();
   ex_->set_copy_block(copy_wgs > 0 ? 256 : 64);
   ex_->set_copy_grid(copy_wgs);
-  if (marks) {
-    marks->mark("main:start", m);
-    ex_->pack(cur, m);
-    marks->mark("main:pack", m);
-    ex_->transfer(m);
-    marks->mark("main:rccl", m);
-    ex_->unpack(cur, m);
-    marks->mark("main:unpack", m);
-  } else {
-    ex_->exchange(cur, m);
-  }
+  if (marks) marks->mark("main:start", m);
+  exchange_marked(cur, m, marks);
   ex_->set_copy_grid(0);
   ex_->set_copy_block(0);
   kernels::stencil5_chunk_pass<T>(cur, nxt, tile_, cfg_.coeffs, hl->outer_shape, hl->outer_table.get(),
@@ -772,14 +723,27 @@ void StencilSolver<T>::enqueue_halo_last(T* cur, T* nxt, HaloLastPass* hl, Marks
 }
 
 template <typename T>
+void StencilSolver<T>::exchange_marked(T* tile, hipStream_t s, Marks* marks) {
+  if (!marks) return ex_->exchange(tile, s);
+  ex_->pack(tile, s);
+  marks->mark("main:pack", s);
+  ex_->transfer(s);
+  marks->mark("main:rccl", s);
+  ex_->unpack(tile, s);
+  marks->mark("main:unpack", s);
+}
+
+template <typename T>
+void StencilSolver<T>::serial_opening(T* cur, T* nxt, int S, Marks* marks) {
+  join_side();
+  exchange_marked(cur, main_.get(), marks);
+  enqueue_bare_pass(cur, nxt, S);
+}
+
+template <typename T>
 void StencilSolver<T>::enqueue_opening(int S, bool advance) {
-  if (HaloLastPass* hl = halo_last_pass(S, true)) {
-    enqueue_halo_last(cur_, nxt_, hl);
-  } else {  // no chunk-list form on this tile: the same one exchange, then the pass
-    join_side();
-    prime_exchange();
-    enqueue_bare_pass(cur_, nxt_, S);
-  }
+  if (HaloLastPass* hl = halo_last_pass(S, true)) enqueue_halo_last(cur_, nxt_, hl);
+  else serial_opening(cur_, nxt_, S);  // no chunk-list form on this tile: the same one exchange, then the pass
   if (advance) std::swap(cur_, nxt_);
 }
 
@@ -796,10 +760,10 @@ void StencilSolver<T>::prepare(int iters) {
   MXS_TRACE_RANGE("stencil.prepare");
   maybe_stall("prepare");
   begin_run(true);
-  Group gr[2];
-  split(iters, gr);
+  BlockGroup gr[2];
+  split(iters, block_, gr);
   // Opening::Auto: decide the opening at the depth of the larger group.
-  const Group& big = gr[0].count >= gr[1].count ? gr[0] : gr[1];
+  const BlockGroup& big = gr[0].count >= gr[1].count ? gr[0] : gr[1];
   if (big.count > 0) choose_opening(big.S);
   if (gr[0].count + gr[1].count >= 2) choose_steady(big.S);
   if (big.count > 0) validate_direct(big.S);
@@ -807,18 +771,15 @@ void StencilSolver<T>::prepare(int iters) {
   // whatever this rank's forms and decisions: one priming exchange when the
   // ring is stale, then per cold size one opening (one exchange) when the
   // interior-first opening is on and one super-step (one exchange).
-  for (const Group& g : gr) {
+  for (const BlockGroup& g : gr) {
     if (g.count <= 0) continue;
-    if (post_exchange() && !ghost_fresh_) {
-      prime_exchange();
-      ghost_fresh_ = true;
-    }
+    if (mode() == SuperstepMode::PostExchange) ensure_ring_fresh();
     (void)graphs_for(g.S, g.count);
     if (std::find(warmed_.begin(), warmed_.end(), g.S) != warmed_.end()) continue;
     // One untimed launch of every kernel of this super-step size: cur -> nxt
     // without swapping (nxt is scratch; the exchanges rewrite cur's ghost ring
     // with the same values a real super-step would).
-    if (halo_last_on_ && post_exchange()) {
+    if (halo_last_on_ && mode() == SuperstepMode::PostExchange) {
       enqueue_opening(g.S, false);
       join_side();
     }
@@ -834,8 +795,8 @@ void StencilSolver<T>::force_opening(Opening o) {
   join_side();
   wait_idle("force_opening");
   if (o == Opening::Auto) {
-    halo_last_on_ = halo_last_allowed_ &&
-                    (opening_choice_ == "interior-first" || (opening_choice_.empty() && cfg_.opening == Opening::InteriorFirst));
+    halo_last_on_ = halo_last_allowed_ && (opening_.choice == Choice::InteriorFirst ||
+                                           (opening_.choice == Choice::Undecided && cfg_.opening == Opening::InteriorFirst));
     return;
   }
   MXS_CHECK(o == Opening::Serial || halo_last_allowed_,
@@ -848,7 +809,8 @@ void StencilSolver<T>::force_steady(Opening o) {
   join_side();
   wait_idle("force_steady");
   if (o == Opening::Auto) {
-    steady_on_ = steady_choice_ == "interior-first" || (steady_choice_.empty() && cfg_.steady == Opening::InteriorFirst);
+    steady_on_ = steady_choice_ == Choice::InteriorFirst ||
+                 (steady_choice_ == Choice::Undecided && cfg_.steady == Opening::InteriorFirst);
     return;
   }
   steady_on_ = o == Opening::InteriorFirst;
@@ -859,20 +821,18 @@ void StencilSolver<T>::warm(int iters, int passes) {
   MXS_TRACE_RANGE("stencil.warm");
   maybe_stall("warm");
   begin_run(true);
-  Group gr[2];
-  split(iters, gr);
-  if (post_exchange() && !ghost_fresh_) {
-    prime_exchange();
-    ghost_fresh_ = true;
-  }
+  BlockGroup gr[2];
+  split(iters, block_, gr);
+  const bool post = mode() == SuperstepMode::PostExchange;
+  if (post) ensure_ring_fresh();
   for (int p = 0; p < passes; ++p)
-    for (const Group& g : gr)
+    for (const BlockGroup& g : gr)
       if (g.count > 0) enqueue_block(cur_, nxt_, g.S);  // cur -> nxt, no swap: state unchanged
   // End on the opening's own shape (cur -> nxt, one exchange on every rank):
   // a short window is that super-step, so its launches (both chunk-list
   // passes, the copies beside them) and both streams are the last thing warmed.
-  if (passes > 0 && halo_last_on_ && post_exchange()) {
-    const Group& first = gr[0].count > 0 ? gr[0] : gr[1];
+  if (passes > 0 && halo_last_on_ && post) {
+    const BlockGroup& first = gr[0].count > 0 ? gr[0] : gr[1];
     join_side();
     enqueue_opening(first.S, false);
   }

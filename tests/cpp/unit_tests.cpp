@@ -1,13 +1,15 @@
 // Host-only unit tests of the C++ core ("Unit tests"): region
 // algebra, accessor indexing, Cartesian neighbour tables, halo-plan
 // aggregation/ordering, the collective decision statistics, the
-// interior-first chunk schedule, the pipeline form rule and the fast-form
-// guard. Run by ctest and by tests/test_cpp_unit.py (and under host ASan/UBSan
-// by scripts/cpu_sanitize.sh).
+// interior-first chunk schedule, the pipeline form rule, the fast-form guard
+// and the solver's call plan. Run by ctest and by tests/test_cpp_unit.py (and
+// under host ASan/UBSan by scripts/cpu_sanitize.sh).
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <initializer_list>
 #include <limits>
 #include <vector>
 #include <set>
@@ -21,6 +23,7 @@
 #include "mxs/kernels/chunk_schedule.hpp"
 #include "mxs/kernels/kernels.hpp"
 #include "mxs/kernels/pipe_form.hpp"
+#include "mxs/runtime/call_plan.hpp"
 #include "mxs/runtime/decision.hpp"
 #include "mxs/topo/cart.hpp"
 
@@ -287,7 +290,138 @@ static void test_fast_form_verdict() {
   EXPECT(kernels::fast_form_safe<float>(C{0.2, 0.2, true, 0.0}, 32));
 }
 
+// plan_call (runtime/call_plan.hpp): the schedule of one run(iters) call.
+static bool plan_is(const CallPlan& p, std::initializer_list<PlanStep> want) {
+  if (p.n_steps != int(want.size())) return false;
+  int i = 0;
+  for (const PlanStep& w : want) {
+    const PlanStep& s = p.steps[i++];
+    if (s.kind != w.kind || s.S != w.S || s.count != w.count) return false;
+  }
+  return true;
+}
+
+static void test_call_plan() {
+  using M = SuperstepMode;
+  using K = StepKind;
+  EXPECT(superstep_mode(true, false, true) == M::Fused);
+  EXPECT(superstep_mode(false, true, true) == M::Direct);
+  EXPECT(superstep_mode(false, false, true) == M::Overlap);
+  EXPECT(superstep_mode(false, false, false) == M::PostExchange);
+  const M modes[4] = {M::Fused, M::Direct, M::Overlap, M::PostExchange};
+  const int blocks[6] = {1, 7, 16, 20, 24, 32};
+  for (int iters = 0; iters <= 100; ++iters)
+    for (int block : blocks)
+      for (M mode : modes)
+        for (int flags = 0; flags < 16; ++flags) {
+          const bool multi = flags & 1, opening = flags & 2, steady = flags & 4, fresh = flags & 8;
+          const CallPlan p = plan_call(iters, block, mode, multi, opening, steady, fresh);
+          const bool post = mode == M::PostExchange;
+          EXPECT(p.n_steps <= CallPlan::kMaxSteps && p.n_blocks <= 2);
+          int sum = 0, supersteps = 0, primes = 0, bares = 0, openings = 0, lo = 1 << 30, hi = 0;
+          for (int i = 0; i < p.n_steps; ++i) {
+            const PlanStep& s = p.steps[i];
+            EXPECT(s.count >= 1 && s.S >= 1 && s.S <= block);
+            if (s.kind == K::Prime) {
+              ++primes;
+              continue;
+            }
+            sum += s.S * s.count;
+            supersteps += s.count;
+            lo = std::min(lo, s.S);
+            hi = std::max(hi, s.S);
+            if (s.kind == K::Bare) ++bares;
+            if (s.kind == K::Opening) openings += s.count;
+          }
+          EXPECT(sum == iters);
+          EXPECT(supersteps == (iters + block - 1) / block);
+          EXPECT(iters == 0 || hi - lo <= 1);  // at most two sizes, differing by one
+          int block_sum = 0, block_steps = 0;
+          for (int i = 0; i < p.n_blocks; ++i) {
+            block_sum += p.blocks[i].S * p.blocks[i].count;
+            block_steps += p.blocks[i].count;
+          }
+          EXPECT(block_sum == iters && block_steps == supersteps);
+          EXPECT(primes <= 1);
+          EXPECT(bares <= 1);
+          EXPECT(bares == 0 || mode == M::PostExchange || mode == M::Direct);
+          EXPECT(openings == 0 || (opening && post));
+          EXPECT((p.label == OpeningLabel::None) == (iters == 0));
+          if (iters == 0) {
+            EXPECT(p.n_steps == 0 && p.exchanges == 0);
+            continue;
+          }
+          const K last = p.steps[p.n_steps - 1].kind;
+          if (mode == M::Fused) EXPECT(p.exchanges == 0 && p.label == OpeningLabel::Fused);
+          if (mode == M::Overlap) EXPECT(p.exchanges == supersteps && p.label == OpeningLabel::Overlap);
+          if (mode == M::Direct) {
+            EXPECT(p.exchanges == (multi ? supersteps - 1 : supersteps) + 1 && p.label == OpeningLabel::Direct);
+            EXPECT((last == K::Bare) == multi);
+          }
+          if (post && multi) {
+            // One exchange per super-step on every rank, whatever was decided. The call ends
+            // on the bare pass, or on the opening where that is the last super-step too:
+            // every super-step of a steady interior-first call, the only one of a short call.
+            EXPECT(p.exchanges == supersteps);
+            EXPECT(p.label == OpeningLabel::Primed && !p.ring_fresh);
+            const bool ends_on_opening = opening && (steady || supersteps == 1);
+            EXPECT(last == (ends_on_opening ? K::Opening : K::Bare));
+            EXPECT(openings == (!opening ? 0 : steady ? supersteps : 1));
+          }
+          if (post && !multi) {
+            // One rank: no bare tail; a stale ring costs one exchange more. Calls that end
+            // on an opening (the steady interior-first schedule's, a stale one-super-step
+            // call's) exchange every super-step's input instead and leave the ring stale.
+            const bool all_openings = opening && (steady || (!fresh && supersteps == 1));
+            EXPECT(bares == 0);
+            EXPECT(p.exchanges == supersteps + (!all_openings && !fresh ? 1 : 0));
+            EXPECT(p.ring_fresh == !all_openings);
+            if (!all_openings) EXPECT(p.label == (fresh ? OpeningLabel::Fresh : OpeningLabel::Primed));
+          }
+        }
+  // Spelled-out calls.
+  CallPlan p = plan_call(20, 20, M::PostExchange, true, true, false, false);
+  EXPECT(plan_is(p, {{K::Opening, 20, 1}}) && p.exchanges == 1 && p.label == OpeningLabel::Primed);
+  EXPECT(p.n_blocks == 1 && p.blocks[0].S == 20 && p.blocks[0].count == 1);
+  p = plan_call(240, 20, M::PostExchange, true, true, false, false);
+  EXPECT(plan_is(p, {{K::Opening, 20, 1}, {K::Prime, 20, 1}, {K::Full, 20, 10}, {K::Bare, 20, 1}}) && p.exchanges == 12);
+  p = plan_call(240, 20, M::PostExchange, true, true, true, false);  // steady: all openings, no bare tail
+  EXPECT(plan_is(p, {{K::Opening, 20, 12}}) && p.exchanges == 12 && !p.ring_fresh);
+  p = plan_call(47, 20, M::PostExchange, true, false, false, false);  // 16 + 16 + 15, the 16s first
+  EXPECT(plan_is(p, {{K::Prime, 16, 1}, {K::Full, 16, 2}, {K::Bare, 15, 1}}) && p.exchanges == 3);
+  EXPECT(p.n_blocks == 2 && p.blocks[0].S == 16 && p.blocks[0].count == 2 && p.blocks[1].S == 15 && p.blocks[1].count == 1);
+  EXPECT(std::string(to_string(p.label, false)) == "serial");
+  p = plan_call(47, 20, M::PostExchange, true, true, false, false);  // the opening takes one of the 16s
+  EXPECT(plan_is(p, {{K::Opening, 16, 1}, {K::Prime, 16, 1}, {K::Full, 16, 1}, {K::Bare, 15, 1}}) && p.exchanges == 3);
+  p = plan_call(31, 24, M::PostExchange, true, true, false, false);  // 16 + 15: the second group primes
+  EXPECT(plan_is(p, {{K::Opening, 16, 1}, {K::Prime, 15, 1}, {K::Bare, 15, 1}}) && p.exchanges == 2);
+  p = plan_call(31, 24, M::PostExchange, true, true, true, false);
+  EXPECT(plan_is(p, {{K::Opening, 16, 1}, {K::Opening, 15, 1}}) && p.exchanges == 2);
+  p = plan_call(30, 24, M::PostExchange, false, false, false, true);  // one rank, fresh ring
+  EXPECT(plan_is(p, {{K::Full, 15, 2}}) && p.exchanges == 2 && p.label == OpeningLabel::Fresh && p.ring_fresh);
+  EXPECT(std::string(to_string(p.label, true)) == "fresh");
+  p = plan_call(30, 24, M::PostExchange, true, false, false, true);  // with peers a fresh ring is primed all the same
+  EXPECT(plan_is(p, {{K::Prime, 15, 1}, {K::Full, 15, 1}, {K::Bare, 15, 1}}) && p.exchanges == 2);
+  p = plan_call(60, 20, M::Direct, true, true, true, false);  // pushes: the priming one + all but the bare tail's
+  EXPECT(plan_is(p, {{K::Full, 20, 2}, {K::Bare, 20, 1}}) && p.exchanges == 3);
+  p = plan_call(60, 20, M::Fused, false, false, false, false);
+  EXPECT(plan_is(p, {{K::Full, 20, 3}}) && p.exchanges == 0 && std::string(to_string(p.label, false)) == "fused");
+  EXPECT(std::string(to_string(OpeningLabel::Primed, true)) == "interior-first" &&
+         std::string(to_string(OpeningLabel::None, true)).empty());
+  // split(): ceil(iters / block) near-equal blocks, the larger size first.
+  BlockGroup g[2];
+  split(20, 24, g);
+  EXPECT(g[0].count == 0 && g[1].S == 20 && g[1].count == 1);
+  split(30, 24, g);
+  EXPECT(g[0].count == 0 && g[1].S == 15 && g[1].count == 2);
+  split(47, 20, g);
+  EXPECT(g[0].S == 16 && g[0].count == 2 && g[1].S == 15 && g[1].count == 1);
+  split(0, 20, g);
+  EXPECT(g[0].count == 0 && g[1].count == 0);
+}
+
 int main() {
+  test_call_plan();
   test_pipe_form();
   test_fast_form_verdict();
   test_regions();

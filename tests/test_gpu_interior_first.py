@@ -364,6 +364,50 @@ def test_steady_interior_first_bitwise_vs_serial(gpu, runs):
     assert torch.equal(a.core_view(), b.core_view())
 
 
+_PLAN_RUNS = (24, 48, 31, 100)  # one super-step, 2 x 24, 16 + 15 (two sizes), 5 x 20
+
+
+@pytest.fixture(scope="module")
+def plan_runs_serial_field(gpu):
+    """The field of a one-rank serial solver after _PLAN_RUNS (computed once)."""
+    b = _loopback(4096, 2048, seed=91, opening="serial", time_block=24)
+    for n in _PLAN_RUNS:
+        b.run(n)
+    b.synchronize()
+    return b.core_view().clone()
+
+
+@pytest.mark.parametrize("steady", ["serial", "interior-first"])
+@pytest.mark.parametrize("opening", ["serial", "interior-first"])
+def test_run_executes_the_call_plan(gpu, plan_runs_serial_field, opening, steady):
+    """run() does what plan_call() (runtime/call_plan.hpp) says for the same
+    inputs, none of them rank-local: the blocks, the number of exchanges and
+    the opening's label, whose "primed" this rank resolves from its own form
+    at the first step's depth. A depth without a chunk-list form (31 = 16 + 15
+    opens at 16 when this tile has none there) runs the plan's Opening steps as
+    exchange + pass: the plan is unchanged, which is what keeps an uneven
+    decomposition's ranks in step. The field is bitwise the serial schedule's."""
+    a = _loopback(4096, 2048, seed=91, opening=opening, steady=steady, rehearse_peers=True, time_block=24)
+    assert a.time_block == 24 and a.solver.multi_rank()
+    resolved = set()
+    for n in _PLAN_RUNS:
+        plan = core().plan_call(n, 24, "post-exchange", multi_rank=True, opening_on=opening == "interior-first",
+                                steady_on=steady == "interior-first", ghost_fresh=False)
+        a.run(n)
+        assert a.last_run_blocks() == plan["blocks"], (n, plan)
+        assert a.solver.last_run_exchanges() == plan["exchanges"] == sum(c for _, c in plan["blocks"]), (n, plan)
+        assert plan["label"] == "primed", (n, plan)
+        want = "interior-first" if a.solver.halo_last(plan["steps"][0][1]) else "serial"
+        assert a.solver.last_run_opening() == want, (n, plan)
+        resolved.add(want)
+        kinds = [k for k, _, _ in plan["steps"]]
+        assert ("opening" in kinds) == (opening == "interior-first"), (n, plan)
+    # The form exists at 24 and 20 on this tile, so an opening that is on was resolved to it.
+    assert ("interior-first" in resolved) == (opening == "interior-first")
+    a.synchronize()
+    assert torch.equal(a.core_view(), plan_runs_serial_field)
+
+
 def test_steady_auto_decision_keeps_the_state(gpu):
     """steady = auto (default): prepare() of a call with two or more super-steps
     times two back-to-back super-steps with the second serial or interior-first
