@@ -112,6 +112,104 @@ __global__ __launch_bounds__(2 * kWavesPerBlock * kWaveSize) void pipe_stamped(
   }
 }
 
+// The production pipeline pass (joint windows, sum form, whole groups only)
+// with per-wave stamps around the block barrier of both stages' main loops
+// (pipe_chunk STAMP; TUNE_FOCUS=blockprio). stamps[4 (8 b + wave) ..]: cycles
+// parked at the block barrier, cycles in the block bodies, s_memtime in / out.
+template <int S0, int S1, int PF, bool WRAP, int LAG1, unsigned BPRIO>
+__global__ __launch_bounds__(2 * kWavesPerBlock * kWaveSize) void pipe_block_stamped(
+    const float* __restrict__ in, float* __restrict__ out, index_t pitch, index_t core_off, index_t W, index_t H,
+    index_t x_begin, index_t x_end, index_t y_begin, index_t y_end, const PipeShares shares, float c0, float c1,
+    unsigned long long* stamps) {
+  const unsigned long long t0 = __builtin_amdgcn_s_memtime();
+  constexpr int G = kWavesPerBlock;
+  using P = PipeShape<S0, S1, PF>;
+  using B = BodySumF32;
+  constexpr int OWG = JointShape<S0, S1, G>::OWG;
+  __shared__ B::V ring[G * P::RING * kWaveSize];
+  const index_t rows = y_end - y_begin;
+  const int wave = threadIdx.x / kWaveSize;
+  const int strip = wave % G, stage = wave / G;
+  index_t a = shares.start[blockIdx.x], b = shares.start[blockIdx.x + 1];
+  BlockStamps bs;
+#pragma unroll 1
+  while (a < b) {
+    const index_t grp = a / rows, q0 = a - grp * rows;
+    const index_t q1 = rows < q0 + (b - a) ? rows : q0 + (b - a);
+    pipe_chunk<B, S0, S1, PF, WRAP, true, G, LAG1, false, BPRIO, true>(in, out, pitch, core_off, W, H,
+                                                                       x_begin + grp * OWG, x_end, y_begin + q0,
+                                                                       y_begin + q1, c0, c1, ring, stage, strip, 0, G, &bs);
+    a += q1 - q0;
+  }
+  const unsigned long long t1 = __builtin_amdgcn_s_memtime();
+  if ((threadIdx.x & (kWaveSize - 1)) == 0) {
+    unsigned long long* p = stamps + (size_t(blockIdx.x) * 2 * G + wave) * 4;
+    p[0] = bs.parked;
+    p[1] = bs.body;
+    p[2] = t0;
+    p[3] = t1;
+  }
+}
+
+// TUNE_FOCUS=blockprio, part 1: `reps` stamped passes of one form and block
+// priority schedule (0 = none); per stage the waves' cycles parked at the block
+// barrier as a share of their lifetime and of their main-loop cycles, medians
+// over passes, with the median workgroup's cycles.
+template <int S0, int S1, int PF, bool WRAP, int LAG1, unsigned BPRIO>
+void block_stamps(const char* name, const float* in, float* out, const TileGeom& g, int reps) {
+  constexpr int G = kWavesPerBlock, OWG = JointShape<S0, S1, G>::OWG;
+  int cus = 0;
+  MXS_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
+  const int blocks = cus;  // one 512-thread workgroup per CU (VGPR-bound)
+  const index_t words = index_t(blocks) * 2 * G * 4;
+  DeviceBuffer<unsigned long long> st(words);
+  std::vector<unsigned long long> h(static_cast<size_t>(words));
+  const float c0 = float(std::pow(0.2, S0 + S1));
+  const index_t groups = (g.width + OWG - 1) / OWG;
+  PipeShares shares = PipeShares::equal((groups * g.height + blocks - 1) / blocks);
+  pipe_starts(groups, g.height, blocks, kernels::pipe_fill_rows(S0, S1, PF, LAG1), &shares);
+  std::vector<double> life_share[2], loop_share[2], wg_c;
+  for (int r = 0; r < reps + 3; ++r) {
+    const float* I = (r & 1) ? out : in;
+    float* O = (r & 1) ? const_cast<float*>(in) : out;
+    pipe_block_stamped<S0, S1, PF, WRAP, LAG1, BPRIO><<<blocks, 2 * kBlock>>>(
+        I, O, g.pitch, g.core_offset(), g.width, g.height, 0, g.width, 0, g.height, shares, c0, 0.2f, st.get());
+    MXS_HIP_CHECK(hipDeviceSynchronize());
+    if (r < 3) continue;
+    MXS_HIP_CHECK(hipMemcpy(h.data(), st.get(), size_t(words) * 8, hipMemcpyDeviceToHost));
+    double parked[2] = {0, 0}, body[2] = {0, 0}, life[2] = {0, 0};
+    std::vector<double> c;
+    for (int b = 0; b < blocks; ++b) {
+      unsigned long long lo = ~0ull, hi = 0;
+      for (int w = 0; w < 2 * G; ++w) {
+        const unsigned long long* p = &h[(size_t(b) * 2 * G + w) * 4];
+        parked[w / G] += double(p[0]);
+        body[w / G] += double(p[1]);
+        life[w / G] += double(p[3] - p[2]);
+        lo = std::min(lo, p[2]);
+        hi = std::max(hi, p[3]);
+      }
+      c.push_back(double(hi - lo));
+    }
+    std::sort(c.begin(), c.end());
+    wg_c.push_back(c[c.size() / 2]);
+    for (int s = 0; s < 2; ++s) {
+      life_share[s].push_back(parked[s] / life[s]);
+      loop_share[s].push_back(parked[s] / (parked[s] + body[s]));
+    }
+  }
+  auto med = [](std::vector<double> v) {
+    std::sort(v.begin(), v.end());
+    return v[v.size() / 2];
+  };
+  std::printf("{\"block_stamps\": \"%s\", \"W\": %ld, \"H\": %ld, \"sched\": \"0x%06x\", \"passes\": %d, "
+              "\"stage0_parked_of_lifetime\": %.4f, \"stage1_parked_of_lifetime\": %.4f, "
+              "\"stage0_parked_of_main_loop\": %.4f, \"stage1_parked_of_main_loop\": %.4f, \"wg_kcycles_median\": %.1f}\n",
+              name, long(g.width), long(g.height), BPRIO, reps, med(life_share[0]), med(life_share[1]),
+              med(loop_share[0]), med(loop_share[1]), med(wg_c) / 1e3);
+  std::fflush(stdout);
+}
+
 // TUNE_FOCUS=fillfit: one pipeline form over rows [0, h) of the ghost-ring
 // tile for several h, `reps` stamped passes each; per h the median over passes
 // of the median / max workgroup cycles and of the pass's span.
@@ -332,20 +430,21 @@ Variant balanced(const float* in, float* out, const TileGeom& g, int per_cu, flo
 
 // Two-stage wave pipeline (S = S0 + S1 levels; 512-thread workgroups).
 template <int S0, int S1, int PF, bool WRAP = true, int PRIO = 0, bool SUM = false, int G = 4, bool XM = false,
-          bool JOINT = false, int LAG1 = 0, int XB = 0>
+          bool JOINT = false, int LAG1 = 0, int XB = 0, unsigned BPRIO = 0>
 Variant pipe(const float* in, float* out, const TileGeom& g, float* tmp = nullptr) {
   int per_cu = 0, cus = 0;
   constexpr int threads = 2 * G * kWaveSize;
   MXS_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-      &per_cu, reinterpret_cast<const void*>(stencil5_stream_pipe_kernel<S0, S1, PF, WRAP, PRIO, float, SUM, G, XM, JOINT, LAG1, XB>),
+      &per_cu, reinterpret_cast<const void*>(stencil5_stream_pipe_kernel<S0, S1, PF, WRAP, PRIO, float, SUM, G, XM, JOINT, LAG1, XB, BPRIO>),
       threads, 0));
   MXS_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0));
   const int blocks = std::max(1, per_cu * cus);
-  char buf[128];
-  std::snprintf(buf, sizeof(buf), "pipe_s%d+%d_pf%d_b%d%s%s%s%s%s%s%s%s", S0, S1, PF, per_cu, WRAP ? "_wrap" : "",
+  char buf[128], bp[16] = "";
+  if (BPRIO != 0) std::snprintf(bp, sizeof(bp), "_bp%06x", BPRIO);
+  std::snprintf(buf, sizeof(buf), "pipe_s%d+%d_pf%d_b%d%s%s%s%s%s%s%s%s%s", S0, S1, PF, per_cu, WRAP ? "_wrap" : "",
                 PRIO == 1 ? "_prio0" : (PRIO == 2 ? "_prio1" : ""), SUM ? "_sum" : "",
                 G == 4 ? "" : (G == 2 ? "_g2" : "_g1"), XM ? "_xcd" : "", JOINT ? "_joint" : "", LAG1 == 3 ? "_lag1" : (LAG1 == 2 ? "_lag1s1" : (LAG1 == 1 ? "_lag1s0" : "")),
-                XB == 1 ? "_perm" : (XB == 7 ? "_ntload" : ""));
+                XB == 1 ? "_perm" : (XB == 7 ? "_ntload" : ""), bp);
   const float c0 = SUM ? float(std::pow(0.2, S0 + S1)) : 0.2f;  // sum form: c0 carries c^S
   auto mk = [=](const float* I, float* O) {
     return [=](hipStream_t s) {
@@ -358,7 +457,7 @@ Variant pipe(const float* in, float* out, const TileGeom& g, float* tmp = nullpt
       PipeShares shares = PipeShares::equal(share);
       if (!XM && G == kWavesPerBlock && pipe_balanced() && blocks <= kMaxShareBlocks)
         pipe_starts(groups, g.height, blocks, kernels::pipe_fill_rows(S0, S1, PF, LAG1), &shares);
-      stencil5_stream_pipe_kernel<S0, S1, PF, WRAP, PRIO, float, SUM, G, XM, JOINT, LAG1, XB><<<blocks, threads, 0, s>>>(
+      stencil5_stream_pipe_kernel<S0, S1, PF, WRAP, PRIO, float, SUM, G, XM, JOINT, LAG1, XB, BPRIO><<<blocks, threads, 0, s>>>(
           I, O, g.pitch, g.core_offset(), g.width, g.height, 0, g.width, 0, g.height, shares, c0, 0.2f);
     };
   };
@@ -504,7 +603,29 @@ int main(int argc, char** argv) {
     fillfit<12, 8, 9, 3>("12+8_pf9_asc", in, out, g, hs, reps);
     return 0;
   }
-  if (focus && std::string(focus) == "stamp") {  // per-wave lifetimes of the default S = 16 rotated kernel
+  if (focus && std::string(focus) == "blockprio") {  // in-block progress priority of the pipeline pass
+    // Part 1: per-wave stamps around the block barrier, without and with the
+    // schedule, for the production 12 + 12 (periodic) and 12 + 8 (ghost-ring)
+    // passes. Part 2: the same passes unstamped, timed in interleaved rounds.
+    constexpr unsigned A = kPipeBlockPrio;
+    block_stamps<12, 12, 6, true, 3, 0>("12+12_wrap", in, out, g, rounds);
+    block_stamps<12, 12, 6, true, 3, A>("12+12_wrap", in, out, g, rounds);
+    block_stamps<12, 8, 6, false, 3, 0>("12+8_ghost", in, out, g, rounds);
+    block_stamps<12, 8, 6, false, 3, A>("12+8_ghost", in, out, g, rounds);
+    vs.clear();
+    const Variant p24 = pipe<12, 12, 6, true, 0, true, 4, false, true, 3>(in, out, g);
+    const Variant p20 = pipe<12, 8, 6, false, 0, true, 4, false, true, 3>(in, out, g);
+    // Priority cannot change a result: bitwise (the check copies the tile to the host: small tiles only).
+    auto same = [&](Variant v, const Variant& plain) {
+      if (W * H <= (index_t(1) << 25)) v.ref = plain.launch;
+      v.tol = 0.f;
+      return v;
+    };
+    vs.push_back(p24);
+    vs.push_back(same(pipe<12, 12, 6, true, 0, true, 4, false, true, 3, 0, A>(in, out, g), p24));
+    vs.push_back(p20);
+    vs.push_back(same(pipe<12, 8, 6, false, 0, true, 4, false, true, 3, 0, A>(in, out, g), p20));
+  } else if (focus && std::string(focus) == "stamp") {  // per-wave lifetimes of the default S = 16 rotated kernel
     int occ = 0, cus = 0;
     MXS_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
         &occ, reinterpret_cast<const void*>(balanced_stamped<16, true, true>), 256, 0));

@@ -342,11 +342,24 @@ bool pipe_split();
 // Whether the most recent stencil launch was a pipeline pass that split its
 // last group.
 bool last_pipe_split();
-// The three switches above as pipe_form_for() takes them.
+// In-block progress priority of the fp32 S = 20 / 24 joint pipeline passes in
+// ascending order, sum and scaled forms (stencil_device.hpp: pipe_chunk BPRIO;
+// pipe_form.hpp: pipe_form_for; default on): the two
+// waves that share a SIMD and a block barrier set their priority from the
+// row's position inside the block, so neither parks at the barrier while the
+// other finishes alone. Off runs the same kernels at equal priority. Bitwise
+// equal output. A setter only: no start-up variable.
+void set_pipe_block_prio(bool on);
+bool pipe_block_prio();
+// Whether the most recent stencil launch was a pipeline pass (one launch or
+// chunk list) that ran with it.
+bool last_pipe_block_prio();
+// The four switches above as pipe_form_for() takes them.
 PipeSwitches pipe_switches();
 // The form of the most recent stencil launch if it was a pipeline pass (one
 // launch or chunk list), else PipeForm{}: one record with
-// last_stencil_dispatch(), last_pipe_lag1() and last_pipe_split().
+// last_stencil_dispatch(), last_pipe_lag1(), last_pipe_split() and
+// last_pipe_block_prio().
 PipeForm last_pipe_form();
 // Fill-aware workgroup shares of the pipeline passes (chunk_schedule.hpp:
 // balanced_starts; default on): a share that crosses a column-group boundary

@@ -42,16 +42,19 @@ struct PipeForm {
 constexpr bool operator==(const PipeForm& a, const PipeForm& b) {
   return a.s0 == b.s0 && a.s1 == b.s1 && a.pf == b.pf && a.joint == b.joint && a.lag1 == b.lag1;
 }
-// The experiment switches (kernels.hpp: set_pipe_joint / _lag1 / _split), all on by default.
+// The experiment switches (kernels.hpp: set_pipe_joint / _lag1 / _split /
+// _block_prio), all on by default.
 struct PipeSwitches {
-  bool joint = true, lag1 = true, split = true;
+  bool joint = true, lag1 = true, split = true, block_prio = true;
 };
 // A pass's form, the evaluation form it runs (a request the form has no kernel
-// for falls back to per step) and whether a narrow last group is split.
+// for falls back to per step), whether a narrow last group is split and whether
+// its waves set their priority from their progress inside each block of rows.
 struct PipeChoice {
   PipeForm form;
   EvalForm eval = EvalForm::PerStep;
   bool split = false;
+  bool block_prio = false;
 };
 
 // With ascending levels fp32 S = 20 runs 8 + 12 below this many columns
@@ -97,6 +100,13 @@ constexpr index_t kJointWide = 12288;
 //
 // The narrow last group splits (stencil_device.hpp: pipe_split_form) in the
 // fp32 12 + 12 ascending form only.
+//
+// In-block progress priority (stencil_device.hpp: pipe_chunk BPRIO,
+// pipe_block_prio_form): the fp32 joint forms in ascending order, S = 20 and
+// 24, in the sum and scaled forms (profiles/pipe_prio). The per-step bodies
+// keep equal priorities: s_setprio fences the instruction scheduler, and with
+// it they grow from 207-217 to 244-256 VGPRs. So do fp64 8 + 8 (HBM-bound) and
+// the descending forms.
 constexpr PipeChoice pipe_form_for(int elem_bytes, int S, EvalForm eval, index_t columns, PipeSwitches on = {}) {
   const bool f32 = elem_bytes == 4;
   PipeChoice c;
@@ -108,6 +118,7 @@ constexpr PipeChoice pipe_form_for(int elem_bytes, int S, EvalForm eval, index_t
     c.form.lag1 = ascend ? kLagBoth : 0;
     c.form.s0 = !f32 ? S / 2 : S >= 32 ? 16 : (S == 20 && ascend && columns < kJointWide) ? 8 : 12;
     c.split = on.split && f32 && c.form.s0 == 12 && S == 24 && ascend;
+    c.block_prio = on.block_prio && f32 && ascend && c.eval != EvalForm::PerStep;
   } else {
     if (c.eval == EvalForm::Scaled) c.eval = EvalForm::PerStep;
     c.form.s0 = (!f32 || c.eval == EvalForm::Sum) ? S / 2 : (S / 2 + 1 < 16 ? S / 2 + 1 : 16);
@@ -150,6 +161,11 @@ struct JointShape {
 template <typename T, int S0, int S1, int G, bool JOINT, int LAG1>
 constexpr bool pipe_split_form() {
   return JOINT && sizeof(T) == 4 && G == 4 && S0 == 12 && S1 == 12 && LAG1 == 3;
+}
+// The forms that have kernels with the in-block progress priority.
+template <typename T, int S0, int S1, bool JOINT, int LAG1, bool SUM>
+constexpr bool pipe_block_prio_form() {
+  return JOINT && SUM && sizeof(T) == 4 && LAG1 == kLagBoth && (S0 + S1 == 20 || S0 + S1 == 24);
 }
 
 }  // namespace detail
@@ -205,12 +221,15 @@ constexpr bool joint_twin_ok() {
   return pipe_owg(f) == J::OWG && pipe_apron(f) == J::LEAD && pipe_read_span(f) == (kPipeStrips - 1) * J::OW0 + 256 &&
          joint_owg(S0, S1, kPipeStrips / 2) == JointShape<S0, S1, kPipeStrips / 2>::OWG &&
          pipe_form_for(4, S0 + S1, EvalForm::Sum, 0, {true, LAG1 != 0, true}).split ==
-             pipe_split_form<float, S0, S1, kPipeStrips, true, LAG1>();
+             pipe_split_form<float, S0, S1, kPipeStrips, true, LAG1>() &&
+         pipe_form_for(4, S0 + S1, EvalForm::Sum, 0, {true, LAG1 != 0}).block_prio ==
+             pipe_block_prio_form<float, S0, S1, true, LAG1, true>() &&
+         !pipe_form_for(4, S0 + S1, EvalForm::PerStep, 0, {true, LAG1 != 0}).block_prio;
 }
 static_assert(joint_twin_ok<8, 12, kLagBoth>() && joint_twin_ok<12, 8, kLagBoth>() && joint_twin_ok<12, 8>() &&
                   joint_twin_ok<12, 12, kLagBoth>() && joint_twin_ok<12, 12>() && joint_twin_ok<12, 16>() &&
                   joint_twin_ok<16, 16>() && joint_twin_ok<8, 8>(),
-              "the run-time shape numbers follow JointShape / pipe_split_form");
+              "the run-time shape numbers follow JointShape / pipe_split_form / pipe_block_prio_form");
 }  // namespace detail
 
 // Output columns per group of the two forms auto_time_block weighs (the

@@ -61,6 +61,7 @@ struct LastLaunch {
   const char* kernel = "none";
   PipeForm form;       // pipeline passes only
   bool split = false;  // the pass split its last group
+  bool block_prio = false;  // the pass ran with the in-block progress priority
 };
 std::mutex g_last_mutex;
 LastLaunch g_last;
@@ -356,6 +357,7 @@ const char* last_stencil_dispatch() { return last_launch().kernel; }
 PipeForm last_pipe_form() { return last_launch().form; }
 bool last_pipe_lag1() { return last_launch().form.lag1 != 0; }
 bool last_pipe_split() { return last_launch().split; }
+bool last_pipe_block_prio() { return last_launch().block_prio; }
 
 namespace {
 std::atomic<int> g_gpu_share{1};
@@ -368,6 +370,7 @@ std::atomic<bool> g_pipe_joint{env_switch("MXS_PIPE_JOINT")};
 std::atomic<bool> g_pipe_lag1{env_switch("MXS_PIPE_LAG1")};
 std::atomic<bool> g_pipe_split{env_switch("MXS_PIPE_SPLIT")};
 std::atomic<bool> g_pipe_balanced{env_switch("MXS_PIPE_BALANCED")};
+std::atomic<bool> g_pipe_block_prio{true};
 }  // namespace
 void set_gpu_share(int processes) { g_gpu_share.store(std::max(1, processes), std::memory_order_relaxed); }
 int gpu_share() { return g_gpu_share.load(std::memory_order_relaxed); }
@@ -377,7 +380,9 @@ void set_pipe_lag1(bool on) { g_pipe_lag1.store(on, std::memory_order_relaxed); 
 bool pipe_lag1() { return g_pipe_lag1.load(std::memory_order_relaxed); }
 void set_pipe_split(bool on) { g_pipe_split.store(on, std::memory_order_relaxed); }
 bool pipe_split() { return g_pipe_split.load(std::memory_order_relaxed); }
-PipeSwitches pipe_switches() { return {pipe_joint(), pipe_lag1(), pipe_split()}; }
+void set_pipe_block_prio(bool on) { g_pipe_block_prio.store(on, std::memory_order_relaxed); }
+bool pipe_block_prio() { return g_pipe_block_prio.load(std::memory_order_relaxed); }
+PipeSwitches pipe_switches() { return {pipe_joint(), pipe_lag1(), pipe_split(), pipe_block_prio()}; }
 void set_pipe_balanced(bool on) { g_pipe_balanced.store(on, std::memory_order_relaxed); }
 bool pipe_balanced_on() { return g_pipe_balanced.load(std::memory_order_relaxed); }
 namespace detail {
@@ -401,9 +406,9 @@ void pipe_starts(index_t groups, index_t rows, int blocks, index_t fill, PipeSha
   out->n = blocks;
   for (int w = 0; w <= blocks; ++w) out->start[w] = int(hit->start[size_t(w)]);
 }
-void note_launch(const char* kernel, const PipeForm& form, bool split) {
+void note_launch(const char* kernel, const PipeForm& form, bool split, bool block_prio) {
   std::lock_guard<std::mutex> lock(g_last_mutex);
-  g_last = LastLaunch{kernel, form, split};
+  g_last = LastLaunch{kernel, form, split, block_prio};
 }
 int resident_workgroups(const void* kernel, int threads, int min_per_cu) {
   static std::mutex mutex;

@@ -1150,13 +1150,56 @@ struct PipeShape {
 // (wave_uniform): with a row range the compiler takes for per-lane, stage 0's
 // row stepping moves to the VALU (+5% VALU per row, and the pass then ends
 // 4% later, with the workgroups of the split group).
+//
+// In-block progress priority (BPRIO != 0). Every SIMD holds one stage-0 and one
+// stage-1 wave of the workgroup, and both meet at the barrier that ends each
+// block of PF rows. At equal priority the VALU arbiter prefers the older wave,
+// which then runs its block ahead, parks at the barrier and leaves its partner
+// to finish alone at the lower single-wave issue rate. With BPRIO a wave sets
+// its priority from the row's position inside the block (block_prio_row), high
+// at the block's first rows and low at its last, so the wave that is behind
+// outranks the wave that is ahead and both reach the barrier together. Main
+// loops only; a wave leaves the chunk at priority 0. s_setprio neither changes
+// a result nor blocks a wave.
+// BPRIO packs the levels, two bits per row: row k of a block runs at
+// (BPRIO >> (12 * stage + 2 * k)) & 3 (kPipeBlockPrio: the production schedule).
+//
+// STAMP (tuner): s_memtime at arrival at and release from each main-loop
+// barrier, summed per wave into *stamps (cycles parked, cycles in the bodies).
+struct BlockStamps {
+  unsigned long long parked = 0, body = 0;
+};
+constexpr unsigned pack_block_prio(int a0, int a1, int a2, int a3, int a4, int a5) {
+  return unsigned(a0 | a1 << 2 | a2 << 4 | a3 << 6 | a4 << 8 | a5 << 10);
+}
+constexpr unsigned kPipeBlockPrio = pack_block_prio(3, 2, 2, 1, 1, 0) * 0x1001u;  // both stages alike
+constexpr int block_prio_level(unsigned sched, int stage, int k) { return int(sched >> (12 * stage + 2 * k)) & 3; }
+__device__ __forceinline__ void set_wave_prio(int level) {
+  switch (level) {  // s_setprio takes an immediate
+    case 3: __builtin_amdgcn_s_setprio(3); break;
+    case 2: __builtin_amdgcn_s_setprio(2); break;
+    case 1: __builtin_amdgcn_s_setprio(1); break;
+    default: __builtin_amdgcn_s_setprio(0); break;
+  }
+}
+// Before row k of a block: the block's first row always sets its level (the
+// wave may come from the warm-up at 0), later rows only where it changes.
+template <unsigned BPRIO, int STAGE>
+__device__ __forceinline__ void block_prio_row(int k) {
+  if constexpr (BPRIO != 0) {
+    if (k == 0 || block_prio_level(BPRIO, STAGE, k) != block_prio_level(BPRIO, STAGE, k - 1))
+      set_wave_prio(block_prio_level(BPRIO, STAGE, k));
+  }
+}
+
 template <typename B, int S0, int S1, int PF, bool WRAP, bool JOINT = false, int G = kWavesPerBlock, int LAG1 = 0,
-          bool SUB = false>
+          bool SUB = false, unsigned BPRIO = 0, bool STAMP = false>
 __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in, typename B::T* __restrict__ out,
                                            index_t pitch, index_t core_off, index_t W, index_t H, index_t xw,
                                            index_t x_end, index_t ys, index_t ye, typename B::T c0, typename B::T c1,
                                            typename B::V* __restrict__ ring, int stage, int strip = 0,
-                                           index_t sync_rows = 0, int gs = G) {
+                                           index_t sync_rows = 0, int gs = G, BlockStamps* stamps = nullptr) {
+  static_assert(BPRIO == 0 || PF <= 6, "a block-priority schedule packs six rows per stage");
   static_assert(!SUB || JOINT, "sub-groups are cut from joint windows");
   static_assert(PF % 3 == 0, "the window rotates through 3 slots: PF must be a multiple of 3");
   using P = PipeShape<S0, S1, PF>;
@@ -1291,10 +1334,13 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
     // counter stepping by PF modulo RING (a 64-bit modulo per block cost ~40
     // scalar instructions).
     int base = ((kWarm - (E0 + D)) % RING + RING) % RING;  // 0, PF or 2 PF
+    unsigned long long released = 0;
+    if constexpr (STAMP) released = __builtin_amdgcn_s_memtime();
 #pragma unroll 1
     for (index_t i = kWarm; i < blocks * PF; i += PF) {
 #pragma unroll
       for (int k = 0; k < PF; ++k) {
+        block_prio_row<BPRIO, 0>(k);
         V top;
         if constexpr (ASC0) {
           const int n = k % 3, o = (k + 1) % 3, m = (k + 2) % 3;
@@ -1324,8 +1370,18 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
         if constexpr (B::kStage0Fence) __builtin_amdgcn_sched_barrier(0);
       }
       base = base + PF < RING ? base + PF : 0;
-      __syncthreads();
+      if constexpr (STAMP) {
+        const unsigned long long arrived = __builtin_amdgcn_s_memtime();
+        __syncthreads();
+        const unsigned long long now = __builtin_amdgcn_s_memtime();
+        stamps->body += arrived - released;
+        stamps->parked += now - arrived;
+        released = now;
+      } else {
+        __syncthreads();
+      }
     }
+    if constexpr (block_prio_level(BPRIO, 0, PF - 1) != 0) __builtin_amdgcn_s_setprio(0);
   } else {
     // Output descriptor over rows [ys, ye) (see stream_chunk_rot).
     const index_t x0w = gx - index_t(lane) * N;  // the window's first column
@@ -1390,6 +1446,8 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
       __syncthreads();
     }
     int base = (kWarm / PF) % 3 * PF;  // ring slot of the block's first row (counter, see stage 0)
+    unsigned long long released = 0;
+    if constexpr (STAMP) released = __builtin_amdgcn_s_memtime();
 #pragma unroll 1
     for (index_t i = kWarm; i < (blocks - T1) * PF; i += PF) {
       V inrow[PF];
@@ -1398,6 +1456,7 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
       base = base + PF < RING ? base + PF : 0;
 #pragma unroll
       for (int k = 0; k < PF; ++k) {
+        block_prio_row<BPRIO, 1>(k);
         const index_t j = i + k;
         V top;
         if constexpr (ASC1) {
@@ -1423,8 +1482,18 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
         const unsigned row_term = r >= 0 && r < rows_i ? unsigned(r) * row_bytes : unsigned(kMaxChunkBytes);
         B::store(top, orsrc, lane_term + row_term, c0);
       }
-      __syncthreads();
+      if constexpr (STAMP) {
+        const unsigned long long arrived = __builtin_amdgcn_s_memtime();
+        __syncthreads();
+        const unsigned long long now = __builtin_amdgcn_s_memtime();
+        stamps->body += arrived - released;
+        stamps->parked += now - arrived;
+        released = now;
+      } else {
+        __syncthreads();
+      }
     }
+    if constexpr (block_prio_level(BPRIO, 1, PF - 1) != 0) __builtin_amdgcn_s_setprio(0);
   }
 }
 
@@ -1479,7 +1548,7 @@ struct PipeShares {
 };
 
 template <int S0, int S1, int PF, bool WRAP, int PRIO = 0, typename T = float, bool SUM = false,
-          int G = kWavesPerBlock, bool XM = false, bool JOINT = false, int LAG1 = 0, int XB = 0>
+          int G = kWavesPerBlock, bool XM = false, bool JOINT = false, int LAG1 = 0, int XB = 0, unsigned BPRIO = 0>
 __global__ __launch_bounds__(2 * G * kWaveSize) void stencil5_stream_pipe_kernel(
     const T* __restrict__ in, T* __restrict__ out, index_t pitch, index_t core_off, index_t W, index_t H,
     index_t x_begin, index_t x_end, index_t y_begin, index_t y_end, const PipeShares shares, T c0, T c1) {
@@ -1535,9 +1604,10 @@ __global__ __launch_bounds__(2 * G * kWaveSize) void stencil5_stream_pipe_kernel
         const index_t q1 = wave_uniform(!sub ? r1 : r1 + half < rows ? r1 + half : rows);
         using J = JointShape<S0, S1, G>;
         static_assert(JointShape<S0, S1, G / 2>::ROW * 2 == J::ROW, "a sub-group's joint row is half the ring row");
-        pipe_chunk<B, S0, S1, PF, WRAP, true, G, LAG1, true>(in, out, pitch, core_off, W, H, x_begin + grp * OWG, x_end,
-                                                             y_begin + q0, y_begin + q1, c0, c1,
-                                                             ring + sub * (J::ROW / 2), stage, sstrip, r1 - r0, G / 2);
+        pipe_chunk<B, S0, S1, PF, WRAP, true, G, LAG1, true, BPRIO>(in, out, pitch, core_off, W, H, x_begin + grp * OWG,
+                                                                    x_end, y_begin + q0, y_begin + q1, c0, c1,
+                                                                    ring + sub * (J::ROW / 2), stage, sstrip, r1 - r0,
+                                                                    G / 2);
         a += r1 - r0;
         continue;
       }
@@ -1545,12 +1615,14 @@ __global__ __launch_bounds__(2 * G * kWaveSize) void stencil5_stream_pipe_kernel
     index_t r1 = rows < r0 + (b - a) ? rows : r0 + (b - a);
     r1 = r1 - r0 > max_rows ? r0 + max_rows : r1;
     if constexpr (JOINT) {
-      pipe_chunk<B, S0, S1, PF, WRAP, true, G, LAG1>(in, out, pitch, core_off, W, H, x_begin + grp * OWG, x_end,
-                                                     y_begin + r0, y_begin + r1, c0, c1, ring, stage, strip);
+      pipe_chunk<B, S0, S1, PF, WRAP, true, G, LAG1, false, BPRIO>(in, out, pitch, core_off, W, H, x_begin + grp * OWG,
+                                                                   x_end, y_begin + r0, y_begin + r1, c0, c1, ring, stage,
+                                                                   strip);
     } else {
       const index_t xw = x_begin + (grp * G + strip) * OW;
-      pipe_chunk<B, S0, S1, PF, WRAP, false, G, LAG1>(in, out, pitch, core_off, W, H, xw, x_end, y_begin + r0,
-                                                      y_begin + r1, c0, c1, ring + strip * P::RING * kWaveSize, stage);
+      pipe_chunk<B, S0, S1, PF, WRAP, false, G, LAG1, false, BPRIO>(in, out, pitch, core_off, W, H, xw, x_end,
+                                                                    y_begin + r0, y_begin + r1, c0, c1,
+                                                                    ring + strip * P::RING * kWaveSize, stage);
     }
     a += r1 - r0;
   }
@@ -1563,9 +1635,10 @@ __global__ __launch_bounds__(2 * G * kWaveSize) void stencil5_stream_pipe_kernel
 // beside the halo exchange, then the ghost-ring chunks). The halo copy kernel
 // (copy2d_batch_kernel, 32 VGPRs) runs beside it: two pass waves per SIMD leave
 // it 32 of the 512 VGPRs in the sum forms (fp32 12 + 8 / 12 + 12: 238, 8 + 12:
-// 225, 8-VGPR granules); the per-step 8 + 12 and fp64 8 + 8 forms (244) leave
-// 16, and their copies take the CUs the inner launch leaves free.
-template <int S0, int S1, int PF, typename T, bool SUM, int LAG1, int XB = 0>
+// 225, 8-VGPR granules; with the block priority 220 and 189); the per-step
+// 8 + 12 and fp64 8 + 8 forms (244) leave 16, and their copies take the CUs the
+// inner launch leaves free.
+template <int S0, int S1, int PF, typename T, bool SUM, int LAG1, int XB = 0, unsigned BPRIO = 0>
 __global__ __launch_bounds__(2 * kWavesPerBlock * kWaveSize) void stencil5_pipe_chunks_kernel(
     const T* __restrict__ in, T* __restrict__ out, index_t pitch, index_t core_off, index_t W, index_t H,
     index_t x_begin, index_t x_end, index_t y_begin, const PassChunk* __restrict__ table, int entries, T c0, T c1) {
@@ -1586,8 +1659,9 @@ __global__ __launch_bounds__(2 * kWavesPerBlock * kWaveSize) void stencil5_pipe_
 #pragma unroll 1
     for (index_t r0 = c.r0; r0 < c.r1; r0 += max_rows) {
       const index_t r1 = c.r1 - r0 > max_rows ? r0 + max_rows : c.r1;
-      pipe_chunk<B, S0, S1, PF, false, true, G, LAG1>(in, out, pitch, core_off, W, H, x_begin + index_t(c.group) * OWG,
-                                                     x_end, y_begin + r0, y_begin + r1, c0, c1, ring, stage, strip);
+      pipe_chunk<B, S0, S1, PF, false, true, G, LAG1, false, BPRIO>(in, out, pitch, core_off, W, H,
+                                                                    x_begin + index_t(c.group) * OWG, x_end, y_begin + r0,
+                                                                    y_begin + r1, c0, c1, ring, stage, strip);
     }
   }
 }

@@ -16,7 +16,8 @@
 namespace mxs {
 namespace kernels {
 namespace detail {
-void note_launch(const char* kernel, const PipeForm& form = {}, bool split = false);  // stencil.hip: the last-launch record
+// stencil.hip: the last-launch record
+void note_launch(const char* kernel, const PipeForm& form = {}, bool split = false, bool block_prio = false);
 }
 
 namespace {

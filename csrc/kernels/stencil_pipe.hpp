@@ -23,7 +23,7 @@ static_assert(kPipeStrips == kWavesPerBlock, "pipe_form.hpp counts the strips of
 static_assert(eval_xb(EvalForm::Scaled) == kScaledBody && eval_xb(EvalForm::Sum) == 0, "EvalForm -> <SUM, XB>");
 
 // stencil.hip: the record behind last_stencil_dispatch() / last_pipe_form().
-void note_launch(const char* kernel, const PipeForm& form = {}, bool split = false);
+void note_launch(const char* kernel, const PipeForm& form = {}, bool split = false, bool block_prio = false);
 
 // Workgroups of `kernel` (at `threads` per workgroup) resident at once on this
 // device, occupancy (at least min_per_cu) x CUs, over the processes sharing the
@@ -76,12 +76,15 @@ void with_pipe_form(const PipeChoice& c, F&& fn) {
   }
 }
 
-template <typename T, int S, bool WRAP, EvalForm EF, int JS0, int LAG1>
+// BP: with the in-block progress priority (pipe_block_prio_form forms only).
+template <typename T, int S, bool WRAP, EvalForm EF, int JS0, int LAG1, bool BP = false>
 constexpr auto pipe_kernel() {
   constexpr PipeForm P = kPerStrip<T, S, EF>;
+  static_assert(!BP || pipe_block_prio_form<T, JS0, S - JS0, (JS0 > 0), LAG1, eval_sum(EF)>(),
+                "no block-priority kernel in this form");
   if constexpr (JS0 > 0)
     return stencil5_stream_pipe_kernel<JS0, S - JS0, P.pf, WRAP, 0, T, eval_sum(EF), kWavesPerBlock, false, true, LAG1,
-                                       eval_xb(EF)>;
+                                       eval_xb(EF), BP ? kPipeBlockPrio : 0u>;
   else
     return stencil5_stream_pipe_kernel<P.s0, P.s1, P.pf, WRAP, 0, T, eval_sum(EF)>;
 }
@@ -122,10 +125,20 @@ void launch_pipe_form(const T* in, T* out, const TileGeom& g, index_t x0, index_
             "stencil5_tb: rows of " << g.pitch * index_t(sizeof(T)) << " bytes leave fewer than " << kMinChunkRows
                                     << " rows per pipeline chunk (buffer-descriptor stores)");
   const KernelCoeffs<T> k = kernel_coeffs(EF, c0, c1, S);
-  pipe_kernel<T, S, WRAP, EF, JS0, LAG1>()<<<blocks, 2 * kBlock, 0, s>>>(
-      in, out, g.pitch, g.core_offset(), g.width, g.height, x0, x1, y0, y1, shares, k.a, k.b);
+  constexpr bool kBlockPrio = pipe_block_prio_form<T, JS0, S - JS0, (JS0 > 0), LAG1, eval_sum(EF)>();
+  MXS_CHECK(!ch.block_prio || kBlockPrio, "stencil5_tb: this pipeline form has no block-priority kernel");
+  auto launch = [&](auto kernel) {
+    kernel<<<blocks, 2 * kBlock, 0, s>>>(in, out, g.pitch, g.core_offset(), g.width, g.height, x0, x1, y0, y1, shares,
+                                         k.a, k.b);
+  };
+  if constexpr (kBlockPrio) {
+    if (ch.block_prio) launch(pipe_kernel<T, S, WRAP, EF, JS0, LAG1, true>());
+    else launch(pipe_kernel<T, S, WRAP, EF, JS0, LAG1>());
+  } else {
+    launch(pipe_kernel<T, S, WRAP, EF, JS0, LAG1>());
+  }
   note_launch(EF == EvalForm::Scaled ? "stream_pipe_scaled" : EF == EvalForm::Sum ? "stream_pipe_sum" : "stream_pipe",
-              ch.form, split_half > 0);
+              ch.form, split_half > 0, ch.block_prio);
 }
 
 template <typename T, int S, bool WRAP, EvalForm EF>

@@ -16,9 +16,13 @@ namespace kernels {
 namespace detail {
 namespace {
 
-template <typename T, int S, EvalForm EF, int JS0, int LAG1>
+// BP: with the in-block progress priority (pipe_block_prio_form forms only).
+template <typename T, int S, EvalForm EF, int JS0, int LAG1, bool BP = false>
 constexpr auto chunks_kernel() {
-  return stencil5_pipe_chunks_kernel<JS0, S - JS0, kPerStrip<T, S, EF>.pf, T, eval_sum(EF), LAG1, eval_xb(EF)>;
+  static_assert(!BP || pipe_block_prio_form<T, JS0, S - JS0, true, LAG1, eval_sum(EF)>(),
+                "no block-priority kernel in this form");
+  return stencil5_pipe_chunks_kernel<JS0, S - JS0, kPerStrip<T, S, EF>.pf, T, eval_sum(EF), LAG1, eval_xb(EF),
+                                     BP ? kPipeBlockPrio : 0u>;
 }
 
 // Calls fn(depth, form) with the compile-time depth and evaluation form; false
@@ -100,12 +104,22 @@ void stencil5_chunk_pass(const T* in, T* out, const TileGeom& g, const Stencil5C
       using K = decltype(tag);
       if constexpr (K::JS0 > 0) {
         const KernelCoeffs<T> k = kernel_coeffs(EF, T(c.center), T(c.neighbor), S);
-        chunks_kernel<T, S, EF, K::JS0, K::LAG1>()<<<sh.blocks, 2 * kBlock, 0, s>>>(
-            in, out, g.pitch, g.core_offset(), g.width, g.height, 0, g.width, 0, table, entries, k.a, k.b);
+        // The priority switch as it stands at this launch, like the one-launch pass.
+        const bool block_prio = pipe_form_for(int(sizeof(T)), S, EF, g.width, pipe_switches()).block_prio;
+        auto launch = [&](auto kernel) {
+          kernel<<<sh.blocks, 2 * kBlock, 0, s>>>(in, out, g.pitch, g.core_offset(), g.width, g.height, 0, g.width, 0,
+                                                  table, entries, k.a, k.b);
+        };
+        if constexpr (pipe_block_prio_form<T, K::JS0, S - K::JS0, true, K::LAG1, eval_sum(EF)>()) {
+          if (block_prio) launch(chunks_kernel<T, S, EF, K::JS0, K::LAG1, true>());
+          else launch(chunks_kernel<T, S, EF, K::JS0, K::LAG1>());
+        } else {
+          launch(chunks_kernel<T, S, EF, K::JS0, K::LAG1>());
+        }
         note_launch(EF == EvalForm::Scaled ? "stream_pipe_scaled_chunks"
                     : EF == EvalForm::Sum  ? "stream_pipe_sum_chunks"
                                            : "stream_pipe_chunks",
-                    sh.form);
+                    sh.form, false, block_prio);
       } else {
         MXS_CHECK(false, "stencil5_chunk_pass: the per-strip layout has no chunk-list form");
       }

@@ -195,6 +195,11 @@ PYBIND11_MODULE(_mxs_hip, m) {
   m.def("pipe_split", &kernels::pipe_split);
   m.def("last_pipe_split", &kernels::last_pipe_split,
         "whether the most recent stencil launch was a pipeline pass that split its last group");
+  m.def("set_pipe_block_prio", &kernels::set_pipe_block_prio, py::arg("on"),
+        "in-block progress priority of the fp32 S = 20 / 24 joint pipeline passes (default on; bitwise equal output)");
+  m.def("pipe_block_prio", &kernels::pipe_block_prio);
+  m.def("last_pipe_block_prio", &kernels::last_pipe_block_prio,
+        "whether the most recent stencil launch was a pipeline pass with the in-block progress priority");
   m.def("set_pipe_balanced", &kernels::set_pipe_balanced, py::arg("on"),
         "fill-aware workgroup shares in the pipeline passes (default on; bitwise equal output)");
   m.def("pipe_balanced", &kernels::pipe_balanced_on);
@@ -342,10 +347,12 @@ PYBIND11_MODULE(_mxs_hip, m) {
         d["js0"] = f.joint ? f.s0 : 0;
         d["lag1"] = f.lag1;
         d["split"] = kernels::last_pipe_split();
+        d["block_prio"] = kernels::last_pipe_block_prio();
         return d;
       },
       "the most recent stencil launch as a pipeline pass (one launch or chunk list): js0 (stage-0 levels of the "
-      "joint windows, 0: per-strip layout or no pipeline pass), lag1 (level-order mask), split (narrow last group)");
+      "joint windows, 0: per-strip layout or no pipeline pass), lag1 (level-order mask), split (narrow last group), "
+      "block_prio (in-block progress priority)");
   m.def(
       "stencil5_tb_held",
       [](std::uintptr_t in, std::uintptr_t out, const TileGeom& g, int steps, index_t x0, index_t x1, index_t y0,

@@ -2,19 +2,22 @@
 level order, ascending at every share length vs the round-5 rule, descending on
 shares past 768 rows. --ab split: the narrow last column group of the S = 24
 pass run as two half-height sub-groups (hip().set_pipe_split) vs as one whole
-group.
+group. --ab prio: the in-block progress priority of the pipeline passes
+(hip().set_pipe_block_prio) vs equal priorities. --null pairs the switch's off
+setting with itself (both sides of a round run "off"): the noise floor the
+on / off ratio is read against.
 
 One process, one solver per tile; each round sets the switch
 (order: hip().set_pipe_lag1, on = ascending everywhere, off = descending
-everywhere; split: hip().set_pipe_split), runs ~200 ms of warm passes and a drained warm pass, then times one window as
+everywhere; split: hip().set_pipe_split; prio: hip().set_pipe_block_prio), runs ~200 ms of warm passes and a drained warm pass, then times one window as
 bench.py does (host clock, enqueue to drained + device sync) with clock stamps
 around it: wall ms, the pass's shader cycles at the slowest XCD's clock and
 the median clock. The order alternates first/second from round to round.
 Prints per tile the paired ratios on / off (asc / desc, split / whole: median,
 notch) of wall time and of cycles.
 
-usage: python scripts/exp/order_ab.py [--ab order|split] [--tiles 32768x32768,16384x16384] [--rounds 12]
-                                      [--steps 20] [--time-block 0]
+usage: python scripts/exp/order_ab.py [--ab order|split|prio] [--null] [--tiles 32768x32768,16384x16384]
+                                      [--rounds 12] [--steps 20] [--time-block 0] [--per-step]
 """
 import argparse
 import json
@@ -46,13 +49,17 @@ def main() -> int:
     p.add_argument("--tiles", default="32768x32768,16384x16384")
     p.add_argument("--rounds", type=int, default=12)
     p.add_argument("--steps", type=int, default=20)
-    p.add_argument("--ab", default="order", choices=["order", "split"])
+    p.add_argument("--ab", default="order", choices=["order", "split", "prio"])
+    p.add_argument("--null", action="store_true", help="pair off with off (the noise floor)")
+    p.add_argument("--per-step", action="store_true", help="the per-step form (sum_form=False)")
     p.add_argument("--time-block", type=int, default=0, help="the solver's time block (0 = auto)")
     args = p.parse_args()
     H = hip()
-    on, off = ("asc", "desc") if args.ab == "order" else ("split", "whole")
-    set_switch = H.set_pipe_lag1 if args.ab == "order" else H.set_pipe_split
-    switch_used = H.last_pipe_lag1 if args.ab == "order" else H.last_pipe_split
+    on, off = {"order": ("asc", "desc"), "split": ("split", "whole"), "prio": ("prio", "equal")}[args.ab]
+    set_switch = {"order": H.set_pipe_lag1, "split": H.set_pipe_split, "prio": H.set_pipe_block_prio}[args.ab]
+    switch_used = {"order": H.last_pipe_lag1, "split": H.last_pipe_split, "prio": H.last_pipe_block_prio}[args.ab]
+    if args.null:
+        on = off + "_b"
     K = H.clock_stamp_slots()
     khz = H.wall_clock_rate_khz()
     stamps = torch.zeros(6 * K, dtype=torch.int64, device="cuda")
@@ -60,13 +67,13 @@ def main() -> int:
     for tile in args.tiles.split(","):
         w, h = (int(v) for v in tile.split("x"))
         st = Stencil2D(StencilConfig(global_width=w, global_height=h, dims="1x1", dtype="f32",
-                                     time_block=args.time_block))
+                                     time_block=args.time_block, sum_form=not args.per_step))
         st.run(args.steps)
         st.prepare(args.steps)
         res = {True: [], False: []}
         for r in range(args.rounds):
             for lag in ((True, False) if r % 2 == 0 else (False, True)):
-                set_switch(lag)
+                set_switch(lag and not args.null)
                 st.warm(args.steps, 0.2, 1)
                 st.synchronize()
                 torch.cuda.synchronize()
@@ -101,7 +108,7 @@ def main() -> int:
                f"wall_{on}_over_{off}": notch([x["wall_ms"] / y["wall_ms"] for x, y in zip(a, d)]),
                f"kcycles_{on}_over_{off}": notch([x["kcycles_slowest"] / y["kcycles_slowest"] for x, y in zip(a, d)]),
                f"mhz_{on}_over_{off}": notch([x["mhz"] / y["mhz"] for x, y in zip(a, d)]),
-               "switch_used": [all(x["used"] for x in a), not any(x["used"] for x in d)],
+               "switch_used": [all(x["used"] for x in a) != args.null, not any(x["used"] for x in d)],
                "kernel": H.last_stencil_dispatch()}
         print(json.dumps(rec), flush=True)
         del st
