@@ -54,7 +54,8 @@ __global__ __launch_bounds__(256) void balanced_stamped(const float* __restrict_
     const index_t xw = x_begin + (grp * kWavesPerBlock + wave) * OW;
     wp.done = a - a0;
     if (xw < x_end)
-      stream_chunk_rot<S, 3, WRAP>(in, out, pitch, core_off, W, H, xw, x_end, y_begin + q0, y_begin + q1, c0, c1, &wp);
+      stream_chunk_fast<BodyRotF32, S, 3, WRAP>(in, out, pitch, core_off, W, H, xw, x_end, y_begin + q0, y_begin + q1, c0,
+                                                c1, &wp);
     a += q1 - q0;
   }
   const unsigned long long r1 = __builtin_amdgcn_s_memrealtime(), t1 = __builtin_amdgcn_s_memtime();

@@ -6,6 +6,7 @@
 // the two-stage pipeline, docs/PERF.md), and the LDS-crossbar bodies (XB = 1).
 #pragma once
 
+#include "../csrc/kernels/stencil_device.hpp"
 #include "../csrc/kernels/stencil_pipe.hpp"
 
 namespace mxs {
@@ -79,16 +80,7 @@ __global__ __launch_bounds__(256) void stencil5_tb_kernel(const T* __restrict__ 
       const V dn = *reinterpret_cast<const V*>(src + base + LP);
       const T left = src[base - 1];
       const T right = src[base + N];
-      V o;
-      o[0] = jac<T>(mid[0], up[0], dn[0], left, mid[1 % N], c0, c1);
-      if constexpr (N == 2) {
-        o[1] = jac<T>(mid[1], up[1], dn[1], mid[0], right, c0, c1);
-      } else {
-#pragma unroll
-        for (int k = 1; k < N - 1; ++k) o[k] = jac<T>(mid[k], up[k], dn[k], mid[k - 1], mid[k + 1], c0, c1);
-        o[N - 1] = jac<T>(mid[N - 1], up[N - 1], dn[N - 1], mid[N - 2], right, c0, c1);
-      }
-      *reinterpret_cast<V*>(dst + base) = o;
+      *reinterpret_cast<V*>(dst + base) = jac_vec<T, V, N>(up, mid, dn, left, right, c0, c1);
     }
     __syncthreads();
     T* t = src;
@@ -113,15 +105,6 @@ __global__ __launch_bounds__(256) void stencil5_tb_kernel(const T* __restrict__ 
     }
   }
 }
-
-
-}  // namespace detail
-}  // namespace kernels
-}  // namespace mxs
-
-namespace mxs {
-namespace kernels {
-namespace detail {
 
 // Three-stage pipeline (tuning): levels 1..S0 on the fetching wave, S0+1..S0+S1
 // on a middle wave (LDS ring in, LDS ring out), the last S2 on the storing wave;
@@ -172,19 +155,9 @@ __device__ __forceinline__ void pipe3_chunk(const typename B::T* __restrict__ in
       lx = gx < last_col ? gx : last_col;
     }
     const T* __restrict__ pin = in + core_off + lx;
-    const index_t last_row = ye + S - 1;
-    index_t next = ys - S;
-    if constexpr (WRAP) next = next < 0 ? next + H : next;
-    auto fetch = [&]() -> V {
-      const V v = B::load(pin + next * pitch);
-      if constexpr (WRAP) {
-        ++next;
-        next = next == H ? 0 : next;
-      } else {
-        next = next < last_row ? next + 1 : next;
-      }
-      return v;
-    };
+    index_t first = ys - S;
+    if constexpr (WRAP) first = first < 0 ? first + H : first;
+    RowFetch<B, WRAP> fetch(pin, pitch, WRAP ? H : ye + S - 1, first);
     V win[3][S0];
 #pragma unroll
     for (int q = 0; q < 3; ++q)
@@ -281,13 +254,7 @@ __device__ __forceinline__ void pipe3_chunk(const typename B::T* __restrict__ in
     }
   } else {
     const V* __restrict__ src = ring_b + lane;
-    const T* obase = out + core_off + (xw - SA) + ys * pitch;
-    const unsigned long long ob = reinterpret_cast<unsigned long long>(obase);
-    const unsigned ob_lo = __builtin_amdgcn_readfirstlane(unsigned(ob)),
-                   ob_hi = __builtin_amdgcn_readfirstlane(unsigned(ob >> 32));
-    T* obase_u = reinterpret_cast<T*>((static_cast<unsigned long long>(ob_hi) << 32) | ob_lo);
-    const int nbytes = __builtin_amdgcn_readfirstlane(int(rows * pitch * index_t(sizeof(T))));
-    const __amdgpu_buffer_rsrc_t orsrc = __builtin_amdgcn_make_buffer_rsrc(obase_u, 0, nbytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t orsrc = chunk_out_rsrc(out + core_off + (xw - SA) + ys * pitch, rows, pitch);
     const bool store_lane = lane >= AL && lane < kWaveSize - AL && gx < x_end && xw < x_end;
     const unsigned lane_off = unsigned(lane) * unsigned(N * sizeof(T));
     const unsigned row_bytes = unsigned(pitch) * unsigned(sizeof(T));
@@ -429,7 +396,6 @@ struct BodySumF64Perm : BodySumF64 {
     return sum_w4d_perm(u, m, d);
   }
 };
-
 
 // fp64 register-pressure variants of the sum body (TUNE_FOCUS=spill in
 // stencil_tune64): XB = 5 enters loaded rows without the copy into fresh

@@ -1,6 +1,6 @@
 // Chunk-list work schedules of the two-stage pipeline passes (host only, no HIP).
 //
-// The persistent pipeline (stencil_device.hpp) gives every workgroup a
+// The persistent pipeline (stencil_pipe_kernels.hpp) gives every workgroup a
 // contiguous range of the linear (column group x rows) space. Two schedules
 // are built here:
 //   * balanced_starts: fill-aware equal-time shares of one whole pass (every
@@ -93,7 +93,7 @@ std::int64_t min_budget(const std::vector<Run>& runs, int blocks, std::int64_t f
 // entries (the last = the length of the space); a workgroup with nothing to do
 // has an empty range. last_rows > 0: the last group's run is only last_rows
 // (<= rows) long — a narrow last column group that the pass runs as two
-// half-height sub-groups side by side (stencil_device.hpp: the split group) —
+// half-height sub-groups side by side (stencil_pipe_kernels.hpp: the split group) —
 // so the space is (groups - 1) * rows + last_rows long; 0 = rows.
 inline std::vector<std::int64_t> balanced_starts(std::int64_t groups, std::int64_t rows, int blocks,
                                                  std::int64_t fill, std::int64_t last_rows = 0) {

@@ -50,7 +50,7 @@ struct Stencil5Coeffs {
   // With center == neighbor (= c, the 5-point average) the S-step kernels may
   // run the sum form: each pass accumulates plain 5-point sums and scales by
   // c^S once when it stores (8 instead of 11 VALU issue slots per 4 fp32 cells
-  // and step; stencil_device.hpp). Equal to the per-step evaluation up to
+  // and step; stencil_bodies.hpp). Equal to the per-step evaluation up to
   // rounding (a few ulp), not bit for bit. With center != neighbor (neighbor
   // != 0) the pipeline passes run the scaled form instead: v' = (n + s + w + e)
   // + (center / neighbor) v per level, neighbor^S once per pass (9 instead of 11
@@ -150,7 +150,7 @@ constexpr int kMaxTimeBlock = 16;
 constexpr int kMaxTimeBlockDeep = 32;
 // Largest chunk (rows x pitch bytes) one workgroup of the streaming kernels
 // stores through a single buffer descriptor: below 2^31 with room for the
-// drop offsets of stencil_device.hpp (a sum of two never wraps).
+// drop offsets of stencil_stream.hpp and stencil_pipe_kernels.hpp (a sum of two never wraps).
 constexpr index_t kMaxChunkBytes = 0x7F000000;
 // The wave pipelines walk a longer share in pieces of at most kMaxChunkBytes;
 // rows must be narrow enough that a piece holds at least this many (each piece
@@ -316,7 +316,7 @@ void stencil5_rect(const T* in, T* out, const TileGeom& g, index_t x0, index_t x
 void set_gpu_share(int processes);
 int gpu_share();
 
-// Joint stage-1 windows in the fp32 two-stage pipeline (stencil_device.hpp:
+// Joint stage-1 windows in the fp32 two-stage pipeline (stencil_pipe_kernels.hpp:
 // JointShape): on by default for time blocks that split into two multiples of
 // 4 levels (S = 20, 24, 28, 32); off runs the per-strip layout (bitwise equal
 // output). MXS_PIPE_JOINT=0 in the environment turns it off at start-up.
@@ -331,7 +331,7 @@ bool pipe_lag1();
 // Whether the most recent stencil launch was a pipeline pass in that order.
 bool last_pipe_lag1();
 // The split narrow last column group of the fp32 S = 24 (12 + 12, ascending)
-// pipeline pass (stencil_device.hpp: pipe_split_form; default on): when at most
+// pipeline pass (stencil_pipe_kernels.hpp: pipe_split_form; default on): when at most
 // 440 columns are left for the last joint group, its workgroups run it as two
 // two-strip sub-groups on half the rows each, so it costs half a group per row
 // (32768 wide: 36.5 group-rows per row instead of 37). Off runs it as a whole
@@ -343,7 +343,7 @@ bool pipe_split();
 // last group.
 bool last_pipe_split();
 // In-block progress priority of the fp32 S = 20 / 24 joint pipeline passes in
-// ascending order, sum and scaled forms (stencil_device.hpp: pipe_chunk BPRIO;
+// ascending order, sum and scaled forms (stencil_pipe_kernels.hpp: pipe_chunk BPRIO;
 // pipe_form.hpp: pipe_form_for; default on): the two
 // waves that share a SIMD and a block barrier set their priority from the
 // row's position inside the block, so neither parks at the barrier while the

@@ -1,4 +1,4 @@
-// The form of a two-stage pipeline pass (stencil_device.hpp:
+// The form of a two-stage pipeline pass (stencil_pipe_kernels.hpp:
 // stencil5_stream_pipe_kernel / stencil5_pipe_chunks_kernel), chosen once for
 // the one-launch and the chunk-list pass: the evaluation form, the stage split,
 // the window layout and the level order, and the shape numbers that follow
@@ -17,7 +17,7 @@ namespace kernels {
 // Derived once per pass (kernels.hpp: eval_form); the only encoding above the
 // kernel template arguments.
 enum class EvalForm : int { PerStep = 0, Sum = 1, Scaled = 2 };
-// The device templates' <SUM, XB> (stencil_device.hpp: FastBody).
+// The device templates' <SUM, XB> (stencil_bodies.hpp: FastBody).
 constexpr bool eval_sum(EvalForm f) { return f != EvalForm::PerStep; }
 constexpr int eval_xb(EvalForm f) { return f == EvalForm::Scaled ? 2 : 0; }
 // Depths at which the scaled form has kernels: the fp32 balanced stream kernel
@@ -32,7 +32,7 @@ constexpr int kLagBoth = 3;     // level-order mask: both stages ascend
 
 // s0 + s1 levels in the two stages, pf input rows in flight; joint: stage 1's
 // windows are cut from one joint row per group (JointShape), else every strip
-// carries the apron of all S levels; lag1: level-order mask (stencil_device.hpp
+// carries the apron of all S levels; lag1: level-order mask (stencil_pipe_kernels.hpp
 // pipe_chunk), 0 = both stages descend, kLagBoth = both ascend.
 struct PipeForm {
   int s0 = 0, s1 = 0, pf = 0;
@@ -98,10 +98,10 @@ constexpr index_t kJointWide = 12288;
 // tie (4,354 vs 4,346 G cells/s, profiles/r06_fp64), so fp64 ascends at every
 // share length too. The other joint depths descend.
 //
-// The narrow last group splits (stencil_device.hpp: pipe_split_form) in the
+// The narrow last group splits (stencil_pipe_kernels.hpp: pipe_split_form) in the
 // fp32 12 + 12 ascending form only.
 //
-// In-block progress priority (stencil_device.hpp: pipe_chunk BPRIO,
+// In-block progress priority (stencil_pipe_kernels.hpp: pipe_chunk BPRIO,
 // pipe_block_prio_form): the fp32 joint forms in ascending order, S = 20 and
 // 24, in the sum and scaled forms (profiles/pipe_prio). The per-step bodies
 // keep equal priorities: s_setprio fences the instruction scheduler, and with

@@ -78,7 +78,7 @@ __device__ __forceinline__ void copy2d_batch_body(T* __restrict__ s0, T* __restr
   // Highest wave priority: in the interior-first opening the pack / unpack run
   // while the inner chunk launch still fills most CUs (a copy wave fits beside a
   // pipeline workgroup: 20 VGPRs), and the pass's VALU-bound waves, which
-  // raise their own priority as they progress (stencil_device.hpp), otherwise
+  // raise their own priority as they progress (stencil_stream.hpp), otherwise
   // win every issue slot: the pack crawled until the pass ended (140 us for
   // 4 MB, profiles/r03_frame). A copy wave issues little: it mostly waits on memory.
   __builtin_amdgcn_s_setprio(3);

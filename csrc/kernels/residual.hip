@@ -6,7 +6,7 @@
 // in the element type (the stencil kernels' expression, then one subtraction),
 // reduced to max |r| and sum r^2 (accumulated in double).
 //
-// Shape (the RegisterRoll body of stencil_device.hpp with the store replaced
+// Shape (the RegisterRoll body of stencil_sweep.hpp with the store replaced
 // by the two accumulations):
 //   * a wave owns a strip of 64 16-byte lane vectors (256 fp32 / 128 fp64
 //     columns), four waves side by side per workgroup, and walks a contiguous
@@ -73,7 +73,7 @@ __device__ __forceinline__ T fma_t(T a, T b, T c) {
   else return __builtin_fmaf(a, b, c);
 }
 
-// Whole-wavefront DPP shifts (stencil_device.hpp): lane i reads lane i - 1
+// Whole-wavefront DPP shifts (stencil_bodies.hpp): lane i reads lane i - 1
 // (wave_shr) or lane i + 1 (wave_shl); the shifted-in lane gets 0.
 constexpr int kDppWaveShl1 = 0x130;
 constexpr int kDppWaveShr1 = 0x138;

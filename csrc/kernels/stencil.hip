@@ -5,7 +5,7 @@
 // traffic per cell (read u, write u') for ~6 flops: HBM-bound by two orders of
 // magnitude. One sweep per iteration therefore tops out at the copy roofline
 // (~0.7 T cells/s fp32); the framework's default path is temporal blocking
-// (stencil5_tb below: the wave-streaming kernels of stencil_device.hpp advance
+// (stencil5_tb below: the wave-streaming kernels of stencil_stream.hpp advance
 // S iterations per pass over HBM, ~6 T cells/s at S = 12). The single-sweep
 // kernels remain for S = 1, remainders and box stencils:
 //
@@ -177,14 +177,14 @@ int balanced_blocks() {
       kBlock, 2);
 }
 
-// Wave-streaming kernels (stencil_device.hpp). Bulk rectangles: the balanced
+// Wave-streaming kernels (stencil_stream.hpp). Bulk rectangles: the balanced
 // persistent launch — as many workgroups as are resident, each streaming an
 // equal share of (4-strip group) x rows (profiles/stencil_tuning/tune16: +12-17%
 // over the grid form on 8192^2 and on the 8-GPU tile 8192 x 16384, equal on
 // 32768^2). Rectangles too small to give every workgroup >= 64 rows use the
 // grid form, whose row chunk CH is the largest of 512..64 that still yields
 // >= 4096 waves.
-// The fp32 rotated-pair form (stream_chunk_rot: 11 VALU per level-row instead
+// The fp32 rotated-pair form (stream_chunk_fast: 11 VALU per level-row instead
 // of ~15, DPP shifts folded into the adds) stores through a buffer descriptor
 // over one chunk's rows: it needs whole output vectors and a chunk of at most
 // kMaxChunkBytes (the balanced kernel walks longer shares in pieces, so there

@@ -1,5 +1,5 @@
 // Device code of the held-side S-step tile (kernels::stencil5_tb_held): the
-// single-buffer LDS tile of stencil_device.hpp (stencil5_tb1_kernel) with fixed
+// single-buffer LDS tile of stencil_tile.hpp (stencil5_tb1_kernel) with fixed
 // boundary values. Like that kernel it stages the tile plus an S-deep apron and
 // updates EVERY staged cell in place at each of the S levels (no shrinking
 // trapezoid), so holding a physical edge only means not writing some cells
@@ -16,7 +16,8 @@
 #include <hip/hip_runtime.h>
 
 #include "mxs/kernels/kernels.hpp"
-#include "stencil_device.hpp"
+#include "stencil_bodies.hpp"
+#include "stencil_tile.hpp"
 
 namespace mxs {
 namespace kernels {

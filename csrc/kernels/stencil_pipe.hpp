@@ -1,4 +1,4 @@
-// Two-stage pipeline launchers (stencil_device.hpp: stencil5_stream_pipe_kernel),
+// Two-stage pipeline launchers (stencil_pipe_kernels.hpp: stencil5_stream_pipe_kernel),
 // compiled in their own translation units (stencil_pipe_f32.hip,
 // stencil_pipe_f64.hip: ~100 kernel instantiations) and called by the shape
 // dispatch in stencil.hip. The form of a pass is chosen by pipe_form_for()
@@ -13,7 +13,7 @@
 #include "mxs/core/error.hpp"
 #include "mxs/kernels/kernels.hpp"
 #include "mxs/runtime/hip_utils.hpp"
-#include "stencil_device.hpp"
+#include "stencil_pipe_kernels.hpp"
 
 namespace mxs {
 namespace kernels {

@@ -1,6 +1,6 @@
 // Chunk-list pipeline pass of the interior-first multi-GPU super-step
 // (kernels.hpp: chunk_pass_shape / stencil5_chunk_pass; device body
-// stencil5_pipe_chunks_kernel in stencil_device.hpp; chunk lists
+// stencil5_pipe_chunks_kernel in stencil_pipe_kernels.hpp; chunk lists
 // kernels/chunk_schedule.hpp). Its form is the one pipe_form_for() gives the
 // one-launch pass over the same ghost-ring tile, through the same table
 // (stencil_pipe.hpp: with_pipe_form), so the split pass runs exactly the kernel

@@ -175,7 +175,7 @@ def jacobi_held_reference(full: torch.Tensor, steps: int, c_center=0.2, c_neighb
 
 def jacobi_sum_reference_global(u: torch.Tensor, steps: int, c: float = 0.2) -> torch.Tensor:
     """One sum-form pass of `steps` levels on the periodic torus, in the exact
-    association of the GPU sum bodies (stencil_device.hpp sum_rot4f / sum_w4d):
+    association of the GPU sum bodies (stencil_bodies.hpp sum_rot4f / sum_w4d):
     v' = (n + s) + h3 with the horizontal 3-sum built from pair sums,
     h3(x) = (u[x] + u[x+1]) + u[x-1] for even x, (u[x-1] + u[x]) + u[x+1] for odd
     x, then one multiply by c^S — c first rounded to the element type as the

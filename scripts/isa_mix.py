@@ -17,16 +17,27 @@ import re
 import sys
 
 
+def kernel_spans(lines):
+    """(symbol, first, last) of every kernel: from the symbol's label to its
+    .end_amdhsa_kernel, both inclusive (shared with scripts/isa_same.py)."""
+    spans, sym, start = [], None, None
+    for i, l in enumerate(lines):
+        m = re.match(r"^([A-Za-z_$][\w$.]*):", l)
+        if m:
+            sym, start = m.group(1), i
+        elif sym is not None and l.strip() == ".end_amdhsa_kernel":
+            spans.append((sym, start, i))
+            sym = None
+    return spans
+
+
 def kernel_lines(path, needle):
     lines = open(path).read().splitlines()
-    start = None
-    for i, l in enumerate(lines):
-        if start is None and l.endswith(":") and needle in l and not l.startswith(".") and "@" not in l.split(":")[0]:
-            start = i
-        elif start is None and re.match(r"^_Z\S*:", l) and needle in l:
-            start = i
-        elif start is not None and l.strip().startswith("s_endpgm"):
-            return lines[start:i + 1], lines[i:i + 400]
+    for sym, start, last in kernel_spans(lines):
+        if needle in sym:
+            for i in range(start, last):
+                if lines[i].strip().startswith("s_endpgm"):
+                    return lines[start:i + 1], lines[i:i + 400]
     raise SystemExit(f"kernel {needle!r} not found")
 
 

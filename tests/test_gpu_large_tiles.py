@@ -1,7 +1,7 @@
 """Tiles whose rows are MiBs wide (sized for 288 GB of HBM3E per GPU). The
 streaming kernels store through one buffer descriptor per call (32-bit
 offsets, kernels.hpp: kMaxChunkBytes), so a workgroup share longer than that
-is walked in pieces (stencil_device.hpp: stencil5_stream_pipe_kernel,
+is walked in pieces (stencil_pipe_kernels.hpp: stencil5_stream_pipe_kernel,
 stencil5_stream_balanced_kernel); before, such tiles threw (the pipeline) or
 fell back to the slower non-rotated kernel (the balanced stream).
 

@@ -1,5 +1,5 @@
 """The in-block progress priority of the fp32 pipeline passes
-(stencil_device.hpp: pipe_chunk BPRIO; kernels::set_pipe_block_prio) under test.
+(stencil_pipe_kernels.hpp: pipe_chunk BPRIO; kernels::set_pipe_block_prio) under test.
 
 Priority must be invisible in the field: every case runs the same solver with
 the switch on and off and compares the two bitwise; the sum-form cases also

@@ -1,5 +1,5 @@
 """The split narrow last column group of the fp32 S = 24 pipeline pass
-(stencil_device.hpp: pipe_split_form) under test.
+(stencil_pipe_kernels.hpp: pipe_split_form) under test.
 
 When at most 440 columns are left for the last joint group of a 12 + 12 pass,
 its workgroups run it as two two-strip sub-groups on half the rows each. Every

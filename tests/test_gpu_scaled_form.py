@@ -1,4 +1,4 @@
-"""The scaled form (csrc/kernels/stencil_device.hpp: scaled_rot4f / scaled_w4d):
+"""The scaled form (csrc/kernels/stencil_bodies.hpp: scaled_rot4f / scaled_w4d):
 5-point Jacobi with unequal coefficients at the sum form's cost. A pass carries
 v_l = u_l / c_n^l, v' = (n + s + w + e) + (c_c / c_n) v, and scales by c_n^S
 once when it stores. Checked against the fp64 PyTorch reference of S plain
