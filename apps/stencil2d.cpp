@@ -36,6 +36,9 @@
 // --loopback, --bind bunch|rrobin,
 // --dump / --no-dump, --checksum, --non-periodic, --block-fixed-edges (with --non-periodic: keep the time
 // block, the frame along the fixed edges on the held-side kernel), --seed S, --json FILE,
+// --relaxation chebyshev (with --non-periodic --block-fixed-edges on a solver backend: every time block is one
+// Chebyshev cycle, kernels/relaxation.hpp; --iters and --check-every in whole cycles, the field is meaningful
+// at cycle ends only; default time block 24 fp32 / 16 fp64),
 // --tol T [--check-every N] (iterate until the linf residual A u - u is <= T, checked every N iterations,
 // default 16 time blocks, with --iters as the cap; prints "converged after K iterations, residual R (linf)"),
 // --checkpoint FILE / --resume FILE (collective MPI-IO global grid file, any
@@ -104,10 +107,15 @@ int run(MpiEnv& env, const Cli& cli, const CartTopology& topo, const DeviceBindi
   const double c_center = cli.get_double("c-center", 0.2), c_neighbor = cli.get_double("c-neighbor", 0.2);
   // --no-sum-form: per-step evaluation everywhere (bitwise equal to the CPU app).
   const bool sum_form = !cli.flag("no-sum-form") && c_center == c_neighbor;
+  const std::string relaxation = cli.get("relaxation", "none");
+  MXS_CHECK(relaxation == "none" || relaxation == "chebyshev", "--relaxation must be none or chebyshev, got " << relaxation);
+  const bool chebyshev = relaxation == "chebyshev";
+  MXS_CHECK(!chebyshev || backend != "mpi-staged", "--relaxation chebyshev runs on the solver backends");
   int time_block =
       (backend == "mpi-staged" || !all_periodic)
           ? 1
-          : int(cli.get_int("time-block", iters > 0 && lw >= 64 && lh >= 64
+          : int(cli.get_int("time-block", chebyshev ? kernels::relaxation_auto_depth(int(sizeof(T)), lw, lh)
+                                          : iters > 0 && lw >= 64 && lh >= 64
                                               ? kernels::auto_time_block(lw, lh, int(sizeof(T)), sum_form)
                                               : 1));
   // The time block sets the ghost depth and the exchanges per call: the same on
@@ -159,6 +167,9 @@ int run(MpiEnv& env, const Cli& cli, const CartTopology& topo, const DeviceBindi
   cfg.coeffs = {c_center, c_neighbor, sum_form};
   cfg.time_block = time_block;
   cfg.block_fixed_edges = block_fixed;
+  cfg.relaxation = chebyshev ? Relaxation::Chebyshev : Relaxation::None;
+  cfg.global_width = gw;
+  cfg.global_height = gh;
   std::unique_ptr<StencilSolver<T>> solver;
   std::unique_ptr<MpiStagedHalo<T>> staged;
   const HaloPlan plan = make_halo_plan(topo, rank, g, true, loopback);
@@ -291,7 +302,8 @@ int run(MpiEnv& env, const Cli& cli, const CartTopology& topo, const DeviceBindi
         conv.iterations += int(n);
       }
     };
-    const long long warmup = cli.get_int("warmup", 10);
+    long long warmup = cli.get_int("warmup", 10);
+    if (chebyshev && solver) warmup = (warmup + solver->time_block() - 1) / solver->time_block() * solver->time_block();  // whole cycles
     steps(warmup);
     if (solver && !fault.armed()) {  // graphs + first launches, untimed
       const long long chunk = check_every > 0 ? check_every : (long long)kDefaultCheckBlocks * solver->time_block();
@@ -340,6 +352,9 @@ int run(MpiEnv& env, const Cli& cli, const CartTopology& topo, const DeviceBindi
           js << ", \"steady_choice\": \"" << to_string(solver->steady_choice()) << "\"";
         if (!solver->direct_state().empty()) js << ", \"direct_halo\": \"" << solver->direct_state() << "\"";
         if (!solver->fixed_edge_note().empty()) js << ", \"fixed_edges\": \"" << solver->fixed_edge_note() << "\"";
+        js << ", \"relaxation\": \"" << relaxation << "\", \"cycle\": " << solver->relaxation_cycle()
+           << ", \"omega_min\": " << solver->relaxation_omega_min() << ", \"omega_max\": " << solver->relaxation_omega_max()
+           << ", \"cycle_growth\": " << solver->relaxation_growth();
       }
       if (until)
         js << ", \"tol\": " << app::fmt(tol) << ", \"converged\": " << (conv.converged ? "true" : "false")
@@ -371,7 +386,7 @@ int main(int argc, char** argv) {
   MpiEnv env(&argc, &argv);
   Cli cli(argc, argv, {"dump", "no-dump", "non-periodic", "strict-square", "no-overlap", "overlap", "no-graph",
                        "loopback", "pageable", "checksum", "halo-last", "no-sum-form",
-                       "no-direct-halo", "block-fixed-edges"});
+                       "no-direct-halo", "block-fixed-edges"});  // --relaxation takes a value
   comm_timeout() = cli.get_double("comm-timeout", 300.0);
   const DeviceBinding dev = bind_device(env, cli.get("bind", "bunch"));
   const int n = env.size();

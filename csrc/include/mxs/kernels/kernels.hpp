@@ -22,6 +22,7 @@
 #include "mxs/kernels/chunk_schedule.hpp"
 #include "mxs/kernels/fixed_edge_split.hpp"
 #include "mxs/kernels/pipe_form.hpp"
+#include "mxs/kernels/relaxation.hpp"
 
 namespace mxs {
 namespace kernels {
@@ -226,6 +227,26 @@ template <typename T>
 void stencil5_tb_held(const T* in, T* out, const TileGeom& g, int steps, index_t x0, index_t x1, index_t y0, index_t y1,
                       Stencil5Coeffs c, unsigned hold, hipStream_t s);
 
+// --------------------------------- level-table passes (Chebyshev relaxation)
+// One pass of t.n levels where level l runs fma(neighbor[l], (n + s) + (w + e),
+// center[l] * c): a Chebyshev cycle (relaxation.hpp). The table's doubles are
+// rounded to T once on the host and travel in the kernel arguments, so a
+// captured launch replays the same table. Depths: relaxation_depth_supported().
+// stencil5_tb_levels keeps the contract of stencil5_tb(..., wrap = false) in the
+// per-step form: the two-stage pipeline in the form pipe_form_for() picks for
+// the uniform per-step pass ("stream_pipe_levels"), or, for a rectangle the
+// pipeline cannot take (no whole 4-cell vectors, thin strips), the held tile
+// with no side held. stencil5_tb_held_levels keeps the contract of
+// stencil5_tb_held ("held_levels"). Both are bitwise equal to t.n single steps
+// with the levels' coefficients.
+static_assert(kMaxLevels == kMaxTimeBlockDeep, "a level table holds the deepest time block");
+template <typename T>
+void stencil5_tb_levels(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1,
+                        const LevelTable& t, hipStream_t s);
+template <typename T>
+void stencil5_tb_held_levels(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1,
+                             const LevelTable& t, unsigned hold, hipStream_t s);
+
 // ------------------------------------- chunk-list pass (interior-first super-step)
 // The S-step pass over chunks of the core of a ghost-ring tile (no wrap) on the
 // two-stage pipeline: workgroup w runs the chunk list table[w * entries ..]
@@ -372,7 +393,8 @@ bool pipe_balanced_on();
 // "stream_pipe" (the two-stage pipeline: fp32 blocks > 16 steps, the one the
 // benchmarks time, and fp64 blocks of 12 / 16 on whole lane vectors), "stream_balanced_rot" (persistent single-wave fp32
 // rotated-pair kernel), "stream_balanced", "stream_grid_rot", "stream_grid", "tb_tile",
-// "roll", "roll_wrap", "lds", "rect" or "box". A record of the host-side
+// "roll", "roll_wrap", "lds", "rect", "box", or a level-table pass:
+// "stream_pipe_levels" (pipeline) or "held_levels" (held tile). A record of the host-side
 // dispatch decision, for tests and result records; graph replays do not update it.
 const char* last_stencil_dispatch();
 

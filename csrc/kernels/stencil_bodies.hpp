@@ -28,6 +28,42 @@ __device__ __forceinline__ T jac(T c, T n, T s, T w, T e, T c0, T c1) {
   return fma_t<T>(c1, (n + s) + (w + e), c0 * c);
 }
 
+// Coefficient sources of the level loops. A uniform pass hands the kernels its
+// two scalars; a level-table pass (Chebyshev relaxation, mxs/kernels/relaxation.hpp)
+// its table, passed by value in the kernel arguments. The level loops ask
+// level_coeff(c, l), in the pipeline with l a compile-time constant once they
+// are unrolled, so a table entry is a scalar load from the kernel-argument
+// segment and a uniform coefficient the scalar it always was. LevelArray: one
+// array per coefficient (the held tile indexes it at run time).
+template <typename T, int S>
+struct LevelArray {
+  T v[S];
+};
+template <typename T>
+__device__ __forceinline__ T level_coeff(T c, int) {
+  return c;
+}
+template <typename T, int S>
+__device__ __forceinline__ T level_coeff(const LevelArray<T, S>& c, int l) {
+  return c.v[l];
+}
+// The pipeline's level source: (c0, c1) of a level side by side, so a level is
+// one aligned SGPR pair (one s_load_dwordx2 / x4) that both the multiply and the
+// FMA of a level read (stencil_pipe_levels.hpp: BodyRotLevelsF32). The level
+// bodies take the pair as their coefficient argument.
+template <typename T>
+struct alignas(2 * sizeof(T)) CoeffPair {
+  T c0, c1;
+};
+template <typename T, int S>
+struct LevelPairs {
+  CoeffPair<T> v[S];
+};
+template <typename T, int S>
+__device__ __forceinline__ CoeffPair<T> level_coeff(const LevelPairs<T, S>& c, int l) {
+  return c.v[l];
+}
+
 constexpr int kWavesPerBlock = 4;
 constexpr int kNumXcds = 8;  // MI355X: workgroups are dealt round-robin over 8 XCDs
 constexpr int kBlock = kWavesPerBlock * kWaveSize;

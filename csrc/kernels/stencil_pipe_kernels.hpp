@@ -83,6 +83,13 @@ struct PipeShape {
 //
 // STAMP (tuner): s_memtime at arrival at and release from each main-loop
 // barrier, summed per wave into *stamps (cycles parked, cycles in the bodies).
+//
+// C: the coefficient source (stencil_bodies.hpp: level_coeff). B::T, the
+// default, is a uniform coefficient; a level table (stencil_pipe_levels.hpp)
+// hands level l of the pass, counted over both stages, its own pair. The level
+// index is a constant in every unrolled level loop below, and with C = B::T the
+// kernels compile to the instructions they had before the parameter existed
+// (scripts/isa_same.py).
 struct BlockStamps {
   unsigned long long parked = 0, body = 0;
 };
@@ -116,10 +123,10 @@ __device__ __forceinline__ void block_barrier(BlockStamps* stamps, unsigned long
 }
 
 template <typename B, int S0, int S1, int PF, bool WRAP, bool JOINT = false, int G = kWavesPerBlock, int LAG1 = 0,
-          bool SUB = false, unsigned BPRIO = 0, bool STAMP = false>
+          bool SUB = false, unsigned BPRIO = 0, bool STAMP = false, typename C = typename B::T>
 __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in, typename B::T* __restrict__ out,
                                            index_t pitch, index_t core_off, index_t W, index_t H, index_t xw,
-                                           index_t x_end, index_t ys, index_t ye, typename B::T c0, typename B::T c1,
+                                           index_t x_end, index_t ys, index_t ye, const C c0, const C c1,
                                            typename B::V* __restrict__ ring, int stage, int strip = 0,
                                            index_t sync_rows = 0, int gs = G, BlockStamps* stamps = nullptr) {
   static_assert(BPRIO == 0 || PF <= 6, "a block-priority schedule packs six rows per stage");
@@ -226,7 +233,7 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
           pf[k] = fetch();
 #pragma unroll
           for (int l = 0; l < S0 - 1; ++l)
-            if (l < b) win[n][l + 1] = B::jac(win[o][l], win[m][l], win[n][l], c0, c1);
+            if (l < b) win[n][l + 1] = B::jac(win[o][l], win[m][l], win[n][l], level_coeff(c0, l), level_coeff(c1, l));
         } else {
           const int p0 = k % 3, p1 = (k + 1) % 3, p2 = (k + 2) % 3;
           const int b = (ib + k) / 3;
@@ -234,7 +241,8 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
           pf[k] = fetch();
 #pragma unroll
           for (int l = S0 - 2; l >= 0; --l)
-            if (l <= b) win[p0][l + 1] = B::jac(win[p0][l], win[p1][l], win[p2][l], c0, c1);
+            if (l <= b)
+              win[p0][l + 1] = B::jac(win[p0][l], win[p1][l], win[p2][l], level_coeff(c0, l), level_coeff(c1, l));
         }
       }
       __syncthreads();
@@ -257,7 +265,7 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
           pf[k] = fetch();
 #pragma unroll
           for (int l = 0; l < S0; ++l) {
-            const V v = B::jac(win[o][l], win[m][l], win[n][l], c0, c1);
+            const V v = B::jac(win[o][l], win[m][l], win[n][l], level_coeff(c0, l), level_coeff(c1, l));
             if (l == S0 - 1) top = v;
             else win[n][l + 1] = v;
           }
@@ -267,7 +275,7 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
           pf[k] = fetch();
 #pragma unroll
           for (int l = S0 - 1; l >= 0; --l) {
-            const V o = B::jac(win[p0][l], win[p1][l], win[p2][l], c0, c1);
+            const V o = B::jac(win[p0][l], win[p1][l], win[p2][l], level_coeff(c0, l), level_coeff(c1, l));
             if (l == S0 - 1) top = o;
             else win[p0][l + 1] = o;
           }
@@ -327,14 +335,17 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
           win[n][0] = inrow[k];
 #pragma unroll
           for (int l = 0; l < S1 - 1; ++l)
-            if (l < b) win[n][l + 1] = B::jac(win[o][l], win[m][l], win[n][l], c0, c1);
+            if (l < b)
+              win[n][l + 1] = B::jac(win[o][l], win[m][l], win[n][l], level_coeff(c0, S0 + l), level_coeff(c1, S0 + l));
         } else {
           const int p0 = k % 3, p1 = (k + 1) % 3, p2 = (k + 2) % 3;
           const int b = (ib + k) / 3;
           win[p2][0] = inrow[k];
 #pragma unroll
           for (int l = S1 - 2; l >= 0; --l)
-            if (l <= b) win[p0][l + 1] = B::jac(win[p0][l], win[p1][l], win[p2][l], c0, c1);
+            if (l <= b)
+              win[p0][l + 1] =
+                  B::jac(win[p0][l], win[p1][l], win[p2][l], level_coeff(c0, S0 + l), level_coeff(c1, S0 + l));
         }
       }
       __syncthreads();
@@ -358,7 +369,7 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
           win[n][0] = inrow[k];
 #pragma unroll
           for (int l = 0; l < S1; ++l) {
-            const V v = B::jac(win[o][l], win[m][l], win[n][l], c0, c1);
+            const V v = B::jac(win[o][l], win[m][l], win[n][l], level_coeff(c0, S0 + l), level_coeff(c1, S0 + l));
             if (l == S1 - 1) top = v;
             else win[n][l + 1] = v;
           }
@@ -367,14 +378,14 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
           win[p2][0] = inrow[k];
 #pragma unroll
           for (int l = S1 - 1; l >= 0; --l) {
-            const V o = B::jac(win[p0][l], win[p1][l], win[p2][l], c0, c1);
+            const V o = B::jac(win[p0][l], win[p1][l], win[p2][l], level_coeff(c0, S0 + l), level_coeff(c1, S0 + l));
             if (l == S1 - 1) top = o;
             else win[p0][l + 1] = o;
           }
         }
         const int r = int(j - E1);
         const unsigned row_term = r >= 0 && r < rows_i ? unsigned(r) * row_bytes : unsigned(kMaxChunkBytes);
-        B::store(top, orsrc, lane_term + row_term, c0);
+        B::store(top, orsrc, lane_term + row_term, level_coeff(c0, 0));
       }
       block_barrier<STAMP>(stamps, released);
     }

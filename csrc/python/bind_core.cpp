@@ -12,6 +12,7 @@
 #include "mxs/halo/plan.hpp"
 #include "mxs/kernels/chunk_schedule.hpp"
 #include "mxs/kernels/fixed_edge_split.hpp"
+#include "mxs/kernels/relaxation.hpp"
 #include "mxs/runtime/call_plan.hpp"
 #include "mxs/runtime/decision.hpp"
 #include "mxs/topo/cart.hpp"
@@ -267,6 +268,22 @@ PYBIND11_MODULE(_mxs_core, m) {
       "time blocking beside fixed edges: the core's interior (x0, x1, y0, y1), shrunk by `steps` on the held sides "
       "(HOLD_* bits; left / right to whole `vec`-cell vectors), and the frame rectangles that cover the rest "
       "(kernels/fixed_edge_split.hpp); an empty interior is (0, 0, 0, 0)");
+  m.def(
+      "chebyshev_cycle",
+      [](long long w, long long h, double c0, double c1, int M) {
+        const kernels::LevelTable t = kernels::chebyshev_cycle(w, h, c0, c1, M);
+        py::dict d;
+        d["n"] = t.n;
+        d["center"] = std::vector<double>(t.center, t.center + t.n);
+        d["neighbor"] = std::vector<double>(t.neighbor, t.neighbor + t.n);
+        d["growth"] = t.growth;
+        return d;
+      },
+      py::arg("global_width"), py::arg("global_height"), py::arg("c_center"), py::arg("c_neighbor"), py::arg("levels"),
+      "the Chebyshev relaxation cycle of `levels` levels for a grid with fixed edges (kernels/relaxation.hpp): "
+      "per-level (center, neighbor) coefficients in Leja order and the prefix-polynomial growth; raises ValueError "
+      "unless c_neighbor != 0 and the spectrum of I - A is positive");
+  m.attr("MAX_LEVELS") = kernels::kMaxLevels;
   m.def("balanced_starts", &kernels::balanced_starts, py::arg("groups"), py::arg("rows"), py::arg("blocks"),
         py::arg("fill"), py::arg("last_rows") = 0,
         "fill-aware linear starts of the pipeline workgroups' shares (blocks + 1 entries); last_rows > 0: the last "

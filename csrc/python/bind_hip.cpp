@@ -370,6 +370,49 @@ PYBIND11_MODULE(_mxs_hip, m) {
       "S Jacobi steps over [x0, x1) x [y0, y1) of a ghost-ring tile beside fixed edges: cells outside the core on a "
       "held side (hold: HOLD_TOP | HOLD_BOTTOM | HOLD_LEFT | HOLD_RIGHT) keep their input value at every level; "
       "per-step form, bitwise equal to S single steps");
+  auto level_table = [](const std::vector<double>& center, const std::vector<double>& neighbor) {
+    if (center.size() != neighbor.size() || center.empty() || int(center.size()) > kernels::kMaxLevels)
+      throw std::invalid_argument("a level table takes 1.." + std::to_string(kernels::kMaxLevels) +
+                                  " (center, neighbor) pairs");
+    kernels::LevelTable t;
+    t.n = int(center.size());
+    for (int l = 0; l < t.n; ++l) {
+      t.center[l] = center[size_t(l)];
+      t.neighbor[l] = neighbor[size_t(l)];
+    }
+    return t;
+  };
+  m.def(
+      "stencil5_tb_levels",
+      [level_table](std::uintptr_t in, std::uintptr_t out, const TileGeom& g, index_t x0, index_t x1, index_t y0,
+                    index_t y1, const std::vector<double>& center, const std::vector<double>& neighbor,
+                    const std::string& dt, std::uintptr_t s) {
+        const kernels::LevelTable t = level_table(center, neighbor);
+        if (parse_dtype(dt) == DType::F32)
+          kernels::stencil5_tb_levels<float>(ptr<float>(in), ptr<float>(out), g, x0, x1, y0, y1, t, strm(s));
+        else
+          kernels::stencil5_tb_levels<double>(ptr<double>(in), ptr<double>(out), g, x0, x1, y0, y1, t, strm(s));
+      },
+      py::arg("src"), py::arg("dst"), py::arg("geom"), py::arg("x0"), py::arg("x1"), py::arg("y0"), py::arg("y1"),
+      py::arg("center"), py::arg("neighbor"), py::arg("dtype") = "f32", py::arg("stream") = 0,
+      "one pass of len(center) levels over [x0, x1) x [y0, y1) of a ghost-ring tile, level l with (center[l], "
+      "neighbor[l]): the per-step stencil5_tb (no wrap) with a level table; fp32 20 / 24 levels, fp64 12 / 16");
+  m.def(
+      "stencil5_tb_held_levels",
+      [level_table](std::uintptr_t in, std::uintptr_t out, const TileGeom& g, index_t x0, index_t x1, index_t y0,
+                    index_t y1, const std::vector<double>& center, const std::vector<double>& neighbor, unsigned hold,
+                    const std::string& dt, std::uintptr_t s) {
+        const kernels::LevelTable t = level_table(center, neighbor);
+        if (parse_dtype(dt) == DType::F32)
+          kernels::stencil5_tb_held_levels<float>(ptr<float>(in), ptr<float>(out), g, x0, x1, y0, y1, t, hold, strm(s));
+        else
+          kernels::stencil5_tb_held_levels<double>(ptr<double>(in), ptr<double>(out), g, x0, x1, y0, y1, t, hold,
+                                                   strm(s));
+      },
+      py::arg("src"), py::arg("dst"), py::arg("geom"), py::arg("x0"), py::arg("x1"), py::arg("y0"), py::arg("y1"),
+      py::arg("center"), py::arg("neighbor"), py::arg("hold") = 15u, py::arg("dtype") = "f32", py::arg("stream") = 0,
+      "stencil5_tb_held with a level table: level l runs (center[l], neighbor[l]); cells outside the core on a held "
+      "side keep their input value at every level");
   m.attr("HOLD_TOP") = unsigned(kernels::kHoldTop);
   m.attr("HOLD_BOTTOM") = unsigned(kernels::kHoldBottom);
   m.attr("HOLD_LEFT") = unsigned(kernels::kHoldLeft);
@@ -562,9 +605,15 @@ PYBIND11_MODULE(_mxs_hip, m) {
                        double graph_max_superstep_us, const std::string& opening, bool rehearse_peers,
                        double min_gain, int halo_max_ctas, int main_priority, int side_priority,
                        double wire_delay_us, const std::string& direct_engine, const std::string& steady,
-                       bool block_fixed_edges) {
+                       bool block_fixed_edges, const std::string& relaxation, index_t global_width,
+                       index_t global_height) {
              SolverConfig cfg;
              cfg.block_fixed_edges = block_fixed_edges;
+             if (relaxation == "none") cfg.relaxation = Relaxation::None;
+             else if (relaxation == "chebyshev") cfg.relaxation = Relaxation::Chebyshev;
+             else throw std::invalid_argument("relaxation must be none or chebyshev, got '" + relaxation + "'");
+             cfg.global_width = global_width;
+             cfg.global_height = global_height;
              cfg.steady = parse_opening(steady, "steady");
              if (direct_engine == "kernel") cfg.direct_engine = PushEngine::Kernel;
              else if (direct_engine == "copy-engine") cfg.direct_engine = PushEngine::CopyEngine;
@@ -612,8 +661,8 @@ PYBIND11_MODULE(_mxs_hip, m) {
            py::arg("graph_max_superstep_us") = 150.0, py::arg("opening") = "auto", py::arg("rehearse_peers") = false,
            py::arg("min_gain") = 0.0, py::arg("halo_max_ctas") = 0, py::arg("main_priority") = -1,
            py::arg("side_priority") = 0, py::arg("wire_delay_us") = 0.0, py::arg("direct_engine") = "kernel",
-           py::arg("steady") = "auto", py::arg("block_fixed_edges") = false,
-           py::keep_alive<1, 7>())
+           py::arg("steady") = "auto", py::arg("block_fixed_edges") = false, py::arg("relaxation") = "none",
+           py::arg("global_width") = 0, py::arg("global_height") = 0, py::keep_alive<1, 7>())
       .def("field_changed", [](SolverHandle& h) { h.visit([](auto& s) { s.field_changed(); }); },
            "the caller wrote the field: re-exchange the ghost ring and re-check the sum form's range next run")
       .def(
@@ -750,6 +799,25 @@ PYBIND11_MODULE(_mxs_hip, m) {
       .def("scaled_form_active",
            [](SolverHandle& h) { return h.visit([](auto& s) { return s.scaled_form_active(); }); })
       .def("sum_form_note", [](SolverHandle& h) { return h.visit([](auto& s) { return s.sum_form_note(); }); })
+      .def("relaxation_note", [](SolverHandle& h) { return h.visit([](auto& s) { return s.relaxation_note(); }); },
+           "the relaxation cycle: which passes run and why, with M, the weights' range and growth ('' without one)")
+      .def("relaxation_info",
+           [](SolverHandle& h) {
+             return h.visit([](auto& s) {
+               py::dict d;
+               const kernels::LevelTable& t = s.relaxation_table();
+               d["cycle"] = s.relaxation_cycle();
+               d["active"] = s.relaxation_active();
+               d["omega_min"] = s.relaxation_omega_min();
+               d["omega_max"] = s.relaxation_omega_max();
+               d["growth"] = s.relaxation_growth();
+               d["center"] = std::vector<double>(t.center, t.center + t.n);
+               d["neighbor"] = std::vector<double>(t.neighbor, t.neighbor + t.n);
+               return d;
+             });
+           },
+           "the agreed relaxation cycle: cycle (levels, 0 without one), active (the level passes run), omega_min, "
+           "omega_max, growth and the per-level (center, neighbor) coefficients")
       .def("last_run_blocks", [](SolverHandle& h) { return h.visit([](auto& s) { return s.last_run_blocks(); }); },
            "(S, count) super-steps the last run() enqueued")
       .def("last_run_exchanges", [](SolverHandle& h) { return h.visit([](auto& s) { return s.last_run_exchanges(); }); },
@@ -801,6 +869,8 @@ PYBIND11_MODULE(_mxs_hip, m) {
             d["iterations"] = r.iterations;
             d["residual"] = r.residual;
             d["checks"] = r.checks;
+            d["check_every"] = r.check_every;
+            d["max_iters"] = r.max_iters;
             d["reason"] = r.reason;
             d["norm"] = norm;
             py::list hist;

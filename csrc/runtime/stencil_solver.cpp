@@ -53,6 +53,26 @@ StencilSolver<T>::StencilSolver(const CartTopology& topo, int rank, const TileGe
   // The main stream gets the higher priority (lower number): its short pack /
   // unpack / boundary launches should not queue behind the long interior sweep.
   block_ = cfg_.kind == StencilKind::Jacobi5 ? std::max(1, cfg_.time_block) : 1;
+  // Chebyshev relaxation: its preconditions are configuration and topology,
+  // the same on every rank, so every rank throws or none does.
+  relax_ = cfg_.relaxation == Relaxation::Chebyshev;
+  if (relax_) {
+    MXS_CHECK(cfg_.kind == StencilKind::Jacobi5,
+              "relaxation = chebyshev needs the 5-point Jacobi stencil (this solver runs the box stencil)");
+    MXS_CHECK(!topo.periodic_rows && !topo.periodic_cols,
+              "relaxation = chebyshev needs fixed edges on both axes: the topology is periodic in "
+                  << (topo.periodic_rows && topo.periodic_cols ? "both axes" : topo.periodic_rows ? "the rows" : "the columns")
+                  << " (the periodic operator is singular)");
+    MXS_CHECK(cfg_.block_fixed_edges,
+              "relaxation = chebyshev needs block_fixed_edges: a cycle is one time-blocked pass beside the fixed edges");
+    MXS_CHECK(cfg_.global_width > 0 && cfg_.global_height > 0,
+              "relaxation = chebyshev needs the global grid size (SolverConfig::global_width / global_height)");
+    kernels::chebyshev_check(cfg_.global_width, cfg_.global_height, cfg_.coeffs.center, cfg_.coeffs.neighbor);
+    // Automatic time block: the deeper cycle unless it exceeds the tile.
+    if (cfg_.time_block <= 0) block_ = kernels::relaxation_auto_depth(int(sizeof(T)), tile_.width, tile_.height);
+    // One coefficient pair per level: the per-step form.
+    cfg_.coeffs.sum_form = false;
+  }
   // Fixed boundary values on a physical edge must not be advanced as cells:
   // time blocking is only exact when every edge is a neighbour's, or
   // (block_fixed_edges) with the frame along the physical sides on the
@@ -81,6 +101,10 @@ StencilSolver<T>::StencilSolver(const CartTopology& topo, int rank, const TileGe
     block_ = int(-v[0]);
   }
   MXS_CHECK(block_ <= kernels::kMaxTimeBlockDeep, "time_block must be <= " << kernels::kMaxTimeBlockDeep);
+  MXS_CHECK(!relax_ || kernels::relaxation_depth_supported(int(sizeof(T)), block_),
+            "relaxation = chebyshev needs an agreed time block of "
+                << (sizeof(T) == 4 ? "20 or 24 (fp32)" : "12 or 16 (fp64)") << ", got " << block_
+                << " (requested " << cfg_.time_block << "; blocks past 16 need fp32 and a tile width of whole 4-cell vectors)");
   MXS_CHECK(block_ <= tile_.width && block_ <= tile_.height,
             "time_block " << block_ << " exceeds the tile (" << tile_.width << "x" << tile_.height
                           << "): its ghost ring would reach past the neighbouring tiles");
@@ -210,6 +234,33 @@ StencilSolver<T>::StencilSolver(const CartTopology& topo, int rank, const TileGe
     sum_note_ = fast_form_note(v);
   }
   cfg_.coeffs.sum_form = user_sum_ && sum_coeffs_ok_;
+  if (relax_) {
+    sum_note_ = "fast form off: relaxation = chebyshev runs the per-step form (one coefficient pair per level)";
+    // The table is computed once, on rank 0, and every rank adopts its bits
+    // (the other ranks contribute zeros to an exact sum), so all tiles run the
+    // same coefficients whatever each host's libm returns.
+    std::vector<double> v(size_t(2 * block_ + 1), 0.0);
+    if (rank == 0) {
+      const kernels::LevelTable t = kernels::chebyshev_cycle(cfg_.global_width, cfg_.global_height, cfg_.coeffs.center,
+                                                             cfg_.coeffs.neighbor, block_);
+      for (int l = 0; l < block_; ++l) {
+        v[size_t(l)] = t.center[l];
+        v[size_t(block_ + l)] = t.neighbor[l];
+      }
+      v[size_t(2 * block_)] = t.growth;
+    }
+    agree_sum(v, "construction: relaxation table agreement");
+    levels_.n = block_;
+    for (int l = 0; l < block_; ++l) {
+      levels_.center[l] = v[size_t(l)];
+      levels_.neighbor[l] = v[size_t(block_ + l)];
+      const double w = kernels::relaxation_omega(levels_, cfg_.coeffs.neighbor, l);
+      omega_min_ = l == 0 ? w : std::min(omega_min_, w);
+      omega_max_ = l == 0 ? w : std::max(omega_max_, w);
+    }
+    levels_.growth = v[size_t(2 * block_)];
+    relax_on_ = true;  // until the range guard says otherwise (ensure_range)
+  }
 }
 
 template <typename T>
@@ -252,13 +303,32 @@ void StencilSolver<T>::update(const T* in, T* out, int steps, index_t c0, index_
 template <typename T>
 void StencilSolver<T>::core_pass(const T* cur, T* nxt, int S, hipStream_t s) {
   const index_t w = tile_.width, h = tile_.height;
-  if (hold_ == 0 || S <= 1) return update(cur, nxt, S, 0, w, 0, h, s);
+  // A relaxation cycle: the same split, the level-table kernels. (A pass of
+  // another depth is a warm-up of prepare() / warm() into scratch: plain.)
+  const bool levels = relax_on_ && S == levels_.n;
+  if (hold_ == 0 || S <= 1) {
+    if (levels) return kernels::stencil5_tb_levels<T>(cur, nxt, tile_, 0, w, 0, h, levels_, s);
+    return update(cur, nxt, S, 0, w, 0, h, s);
+  }
   const kernels::FixedEdgeSplit sp = kernels::fixed_edge_split(w, h, S, kFixedEdgeVec, hold_);
-  update(cur, nxt, S, sp.interior.x0, sp.interior.x1, sp.interior.y0, sp.interior.y1, s);
+  const kernels::Rect& in = sp.interior;
+  if (levels) kernels::stencil5_tb_levels<T>(cur, nxt, tile_, in.x0, in.x1, in.y0, in.y1, levels_, s);
+  else update(cur, nxt, S, in.x0, in.x1, in.y0, in.y1, s);
   for (int i = 0; i < sp.n_frame; ++i) {
     const kernels::Rect& f = sp.frame[i];
-    kernels::stencil5_tb_held<T>(cur, nxt, tile_, S, f.x0, f.x1, f.y0, f.y1, cfg_.coeffs, hold_, s);
+    if (levels) kernels::stencil5_tb_held_levels<T>(cur, nxt, tile_, f.x0, f.x1, f.y0, f.y1, levels_, hold_, s);
+    else kernels::stencil5_tb_held<T>(cur, nxt, tile_, S, f.x0, f.x1, f.y0, f.y1, cfg_.coeffs, hold_, s);
   }
+}
+
+template <typename T>
+std::string StencilSolver<T>::relaxation_note() const {
+  if (!relax_) return "";
+  char buf[256];
+  std::snprintf(buf, sizeof(buf), "chebyshev: M = %d, omega in [%.4g, %.4g], growth %.4g; ", levels_.n, omega_min_,
+                omega_max_, levels_.growth);
+  if (relax_on_) return std::string(buf) + "level passes (the field is meaningful at cycle ends only)";
+  return std::string(buf) + "plain per-step passes: " + relax_guard_;
 }
 
 template <typename T>
@@ -467,7 +537,8 @@ void StencilSolver<T>::prime() {
 
 template <typename T>
 void StencilSolver<T>::ensure_range(bool collective) {
-  if (!(user_sum_ && sum_coeffs_ok_)) return;  // config-level: the same on every rank
+  const bool sum = user_sum_ && sum_coeffs_ok_;
+  if (!sum && !relax_) return;  // config-level: the same on every rank
   // max|u| over the whole current buffer (core, ghost ring and the zeroed
   // padding): with 5 |c| <= 1 no later pass can exceed it, so one local
   // measurement per field change.
@@ -498,6 +569,23 @@ void StencilSolver<T>::ensure_range(bool collective) {
     range_agreed_ = true;
     agreed = true;
   }
+  // Relaxation cycle: inside a cycle the field strays by up to growth x max|u|
+  // (the held boundary ring is part of the measured buffer). Past max(T) / 4
+  // the plain per-step pass runs instead; like the fast forms, a rank-local
+  // measurement may only switch the cycle off.
+  if (relax_) {
+    const bool fits = kernels::relaxation_range_ok<T>(levels_, md) && (agreed || relax_on_);
+    if (fits != relax_on_) {
+      relax_on_ = fits;
+      char buf[160];
+      std::snprintf(buf, sizeof(buf), "growth %.4g x max|u| %.4g is not below max(T) / 4 (range guard)", levels_.growth, md);
+      relax_guard_ = fits ? "" : buf;
+      wait_idle("relaxation range guard");
+      graphs_.clear();  // captured for the other kernels
+      warmed_.clear();
+    }
+  }
+  if (!sum) return;
   // The bound the kernels re-check per pass (kernels::fast_form_verdict), with
   // the agreed range: whenever it holds here it holds there (S <= block_).
   cfg_.coeffs.range = md;
@@ -534,6 +622,9 @@ void StencilSolver<T>::run(int iters) {
   last_opening_form_ = false;
   last_forks_ = 0;
   if (iters <= 0) return;
+  MXS_CHECK(!relax_ || iters % block_ == 0,
+            "run(" << iters << "): with relaxation = chebyshev the cycle is the unit of progress, so the iteration "
+                   << "count must be a multiple of the cycle length " << block_);
   maybe_stall("run");
   begin_run(false);
   // What the call consists of is decided here, from nothing rank-local
@@ -909,9 +1000,15 @@ RunUntil StencilSolver<T>::run_until(double tol, int max_iters, int check_every,
   MXS_CHECK(tol >= 0.0, "run_until: tol must be >= 0, got " << tol);
   MXS_CHECK(max_iters >= 0, "run_until: max_iters must be >= 0, got " << max_iters);
   MXS_CHECK(check_every >= 0, "run_until: check_every must be >= 0 (0: " << kDefaultCheckBlocks << " x time_block), got " << check_every);
-  const int every = check_every > 0 ? check_every : kDefaultCheckBlocks * block_;
+  int every = check_every > 0 ? check_every : kDefaultCheckBlocks * block_;
+  if (relax_) {  // whole cycles: the chunk up, the cap down
+    every = (every + block_ - 1) / block_ * block_;
+    max_iters = max_iters / block_ * block_;
+  }
   const char* name = norm == Norm::Linf ? "linf" : "l2";
   RunUntil out;
+  out.check_every = every;
+  out.max_iters = max_iters;
   for (;;) {
     const Residual r = residual();
     ++out.checks;

@@ -75,6 +75,16 @@ class StencilConfig:
     # in the ghost ring fixed at every level. With sum_form=False the result is
     # bitwise the one-exchange-per-iteration one.
     block_fixed_edges: bool = False
+    # "chebyshev": every block of M iterations is one M-point Chebyshev cycle of
+    # the Jacobi relaxation (ops.chebyshev_cycle: level l of a pass runs its own
+    # coefficient pair), which reaches a tolerance in 10-30x fewer sweeps than
+    # plain Jacobi. Needs jacobi5 and periodic=False; on GPU also
+    # block_fixed_edges and a time block with level kernels (fp32 20 / 24, fp64
+    # 12 / 16; time_block=0 picks 24 / 16). The cycle is the unit of progress:
+    # run(K) needs K % M == 0 and the field is only meaningful at cycle ends.
+    # fp32 stalls at a rounding floor (docs/ARCHITECTURE.md); use f64 for tight
+    # tolerances. "none": plain Jacobi.
+    relaxation: str = "none"
     seed: int = 1234
     init: str = "random"             # random | rank
     graph_supersteps: int = 0        # super-steps per hipGraph launch (0 = auto, ~1 ms of work)
@@ -126,7 +136,8 @@ class StencilConfig:
     _CHOICES = {"prefer": ("wide", "mpi"), "dtype": tuple(_DTYPES), "kind": ("jacobi5", "box"),
                 "backend": ("auto", "rccl", "ipc", "local", "torch"), "variant": ("auto", "roll", "lds"),
                 "init": ("random", "rank"), "direct_engine": ("kernel", "copy-engine"),
-                "opening": ("auto", "serial", "interior-first"), "steady": ("auto", "serial", "interior-first")}
+                "opening": ("auto", "serial", "interior-first"), "steady": ("auto", "serial", "interior-first"),
+                "relaxation": ("none", "chebyshev")}
 
     def __post_init__(self):
         for name, allowed in self._CHOICES.items():
@@ -137,6 +148,14 @@ class StencilConfig:
                              f"got {self.direct_halo!r}")
         if self.global_width <= 0 or self.global_height <= 0:
             raise ValueError("StencilConfig: the global grid must be non-empty")
+        if self.relaxation == "chebyshev":
+            if self.kind != "jacobi5":
+                raise ValueError("StencilConfig: relaxation='chebyshev' needs kind='jacobi5'")
+            if self.periodic:
+                raise ValueError("StencilConfig: relaxation='chebyshev' needs periodic=False (fixed edges on all four "
+                                 "sides: the periodic operator is singular)")
+            if self.init == "rank":
+                raise ValueError("StencilConfig: relaxation='chebyshev' does not run the reference's exchange-only init")
         if not 0.0 <= self.min_gain < 1.0 or self.wire_delay_us < 0 or self.halo_max_ctas < 0:
             raise ValueError("StencilConfig: min_gain in [0, 1), wire_delay_us >= 0, halo_max_ctas >= 0")
 
@@ -164,6 +183,12 @@ class Stencil2D:
         # exchange-only run (its dumps show a stencil_width/2 ghost ring).
         # A ghost ring deeper than a neighbour's tile would need cells two tiles away.
         tb = cfg.time_block
+        # A relaxation cycle is one time block: the deeper level kernels' depth
+        # unless it exceeds the tile (the native solver's rule).
+        self.relaxation = cfg.relaxation == "chebyshev"
+        if self.relaxation and tb <= 0 and dev.type == "cuda":
+            big, small = (24, 20) if cfg.dtype == "f32" else (16, 12)
+            tb = int(self.ctx.allreduce_min(big if big <= min(d.width, d.height) else small))
         # A fast form may run: the sum form (equal coefficients) or the scaled
         # form (unequal, c_neighbor != 0); both take the same time blocks.
         self.sum_form = bool(cfg.sum_form and (cfg.c_center == cfg.c_neighbor or cfg.c_neighbor != 0.0))
@@ -246,13 +271,28 @@ class Stencil2D:
                                           cfg.graph_max_superstep_us, cfg.opening, cfg.rehearse_peers, cfg.min_gain,
                                           cfg.halo_max_ctas, cfg.main_priority, cfg.side_priority,
                                           cfg.wire_delay_us, cfg.direct_engine, cfg.steady,
-                                          block_fixed_edges=bool(cfg.block_fixed_edges and not cfg.periodic))
+                                          block_fixed_edges=bool(cfg.block_fixed_edges and not cfg.periodic),
+                                          relaxation=cfg.relaxation, global_width=cfg.global_width,
+                                          global_height=cfg.global_height)
             # The solver may cap the request (blocks > 16 need the fp32 pipeline's
             # preconditions); the ghost ring was sized for the request.
             self.time_block = self.solver.time_block()
+            self.cycle = int(self.solver.relaxation_info()["cycle"])
         else:
             self.plan = make_plan(d, self.geom, corners=True)
             self.halo = TorchHalo(self.plan, self.ctx)
+            self.cycle = 0
+            if self.relaxation:
+                # The same schedule one iteration at a time: iteration t runs
+                # level t mod M through ops.stencil5. The table is the native
+                # function's, rank 0's bits on every rank.
+                import struct
+
+                self.cycle = cfg.time_block if cfg.time_block > 1 else (24 if cfg.dtype == "f32" else 16)
+                t = C.chebyshev_cycle(cfg.global_width, cfg.global_height, cfg.c_center, cfg.c_neighbor, self.cycle)
+                blob = struct.pack(f"<{2 * self.cycle + 1}d", *t["center"], *t["neighbor"], t["growth"])
+                v = struct.unpack(f"<{2 * self.cycle + 1}d", self.ctx.allgather_bytes(blob)[0])
+                self._levels = (list(v[:self.cycle]), list(v[self.cycle:2 * self.cycle]), v[-1])
 
     # ---------------------------------------------------------------- setup
     def _direct_mode(self, backend: str) -> str:
@@ -339,13 +379,17 @@ class Stencil2D:
     def run(self, iters: int):
         if iters <= 0:
             return
-        self.iteration += iters
+        if self.cycle and iters % self.cycle:
+            raise ValueError(f"run({iters}): with relaxation='chebyshev' the cycle is the unit of progress, so the "
+                             f"iteration count must be a multiple of the cycle length {self.cycle}")
         if self.solver is not None:
             self.solver.run(iters)
+            self.iteration += iters
             return
         self._last_iters = iters
         for _ in range(iters):
             self._python_step()
+            self.iteration += 1
 
     def prepare(self, iters: int):
         """Collective: take every one-off cost of a later ``run(iters)`` now
@@ -380,9 +424,37 @@ class Stencil2D:
         self.halo.exchange(self._cur)
         if cfg.kind == "box":
             ops.stencil_box(self._cur, self._nxt, g, 0, g.width, 0, g.height, cfg.box_weights)
+        elif self.cycle:  # level t mod M of the cycle
+            lvl = self.iteration % self.cycle
+            ops.stencil5(self._cur, self._nxt, g, 0, g.height, self._levels[0][lvl], self._levels[1][lvl])
         else:
             ops.stencil5(self._cur, self._nxt, g, 0, g.height, cfg.c_center, cfg.c_neighbor)
         self._cur, self._nxt = self._nxt, self._cur
+
+    def relaxation_note(self) -> str:
+        """The relaxation cycle: which passes run and why (the level passes, or the
+        plain per-step pass when the range guard growth x max|u| < max(T) / 4
+        fails), with M, the weights' range and the prefix growth ('' for plain
+        Jacobi)."""
+        if self.solver is not None:
+            return self.solver.relaxation_note()
+        if not self.cycle:
+            return ""
+        info = self.relaxation_info()
+        return (f"chebyshev: M = {self.cycle}, omega in [{info['omega_min']:.4g}, {info['omega_max']:.4g}], "
+                f"growth {info['growth']:.4g}; one level per iteration through ops.stencil5 (the field is meaningful "
+                "at cycle ends only)")
+
+    def relaxation_info(self) -> dict:
+        """``{"cycle", "omega_min", "omega_max", "growth"}`` of the agreed cycle
+        (cycle 0 for plain Jacobi)."""
+        if self.solver is not None:
+            i = self.solver.relaxation_info()
+            return {k: i[k] for k in ("cycle", "omega_min", "omega_max", "growth")}
+        if not self.cycle:
+            return {"cycle": 0, "omega_min": 0.0, "omega_max": 0.0, "growth": 0.0}
+        omega = [n / self.cfg.c_neighbor for n in self._levels[1]]
+        return {"cycle": self.cycle, "omega_min": min(omega), "omega_max": max(omega), "growth": self._levels[2]}
 
     # ---------------------------------------------------------- convergence
     MAX_RESIDUAL_HISTORY = 4096  # checks kept in run_until()'s history (StencilSolver: kMaxResidualHistory)
@@ -424,7 +496,9 @@ class Stencil2D:
         ``DEFAULT_CHECK_BLOCKS`` (16) x the time block. Every rank stops at the same iteration. Returns
         ``{"converged", "iterations", "residual", "checks", "reason", "norm",
         "history": [(iteration, linf, l2), ...]}``; ``self.iteration`` advances
-        by the iterations actually run."""
+        by the iterations actually run. With relaxation='chebyshev'
+        ``check_every`` is rounded up and ``max_iters`` down to whole cycles;
+        the result's ``"check_every"`` and ``"max_iters"`` are the values used."""
         if self.cfg.kind != "jacobi5":
             raise ValueError("run_until: only the 5-point Jacobi stencil has a residual (kind is 'box')")
         if norm not in ("linf", "l2"):
@@ -438,9 +512,12 @@ class Stencil2D:
             out["history"] = [tuple(h) for h in out["history"]]
             self.iteration += out["iterations"]
             return out
-        every = check_every if check_every > 0 else self.DEFAULT_CHECK_BLOCKS * self.time_block
-        out = {"converged": False, "iterations": 0, "residual": 0.0, "checks": 0, "reason": "", "norm": norm,
-               "history": []}
+        every = check_every if check_every > 0 else self.DEFAULT_CHECK_BLOCKS * max(self.time_block, self.cycle)
+        if self.cycle:  # whole cycles: the chunk up, the cap down
+            every = -(-every // self.cycle) * self.cycle
+            max_iters = max_iters // self.cycle * self.cycle
+        out = {"converged": False, "iterations": 0, "residual": 0.0, "checks": 0, "check_every": every,
+               "max_iters": max_iters, "reason": "", "norm": norm, "history": []}
         while True:
             r = self.residual()
             out["checks"] += 1
@@ -698,6 +775,9 @@ def main(argv=None) -> int:
     p.add_argument("--block-fixed-edges", action="store_true",
                    help="with --non-periodic: keep the time block (interior on the usual kernels, the frame along "
                         "the fixed edges on the held-side kernel) instead of one exchange per iteration")
+    p.add_argument("--relaxation", default="none", choices=["none", "chebyshev"],
+                   help="chebyshev: each time block is one Chebyshev cycle (needs --non-periodic --block-fixed-edges; "
+                        "--iters, --warmup and --check-every in whole cycles; the field is meaningful at cycle ends)")
     p.add_argument("--tol", type=float, default=None,
                    help="iterate until the residual norm is <= TOL (run_until) instead of --iters iterations; "
                         "the timed region is the run_until")
@@ -722,17 +802,19 @@ def main(argv=None) -> int:
                         loopback=args.loopback, variant=args.variant, time_block=args.time_block,
                         seed=args.seed, opening=args.opening, steady=args.steady, c_center=args.c_center,
                         c_neighbor=args.c_neighbor, sum_form=not args.no_sum_form, periodic=not args.non_periodic,
-                        block_fixed_edges=args.block_fixed_edges)
+                        block_fixed_edges=args.block_fixed_edges, relaxation=args.relaxation)
     st = Stencil2D(cfg, ctx)
     if args.resume:
         hdr = st.load_checkpoint(args.resume)
         if ctx.is_root:
             print(f"resumed from {args.resume} at iteration {hdr.iteration}", file=sys.stderr)
-    st.run(args.warmup)
+    st.run(-(-args.warmup // st.cycle) * st.cycle if st.cycle else args.warmup)  # a relaxation cycle: whole cycles
     until = None
     if args.tol is not None:
         cap = args.iters if args.max_iters is None else args.max_iters
         chunk = args.check_every if args.check_every > 0 else Stencil2D.DEFAULT_CHECK_BLOCKS * st.time_block
+        if st.cycle:  # run_until's own rounding to whole cycles
+            chunk, cap = -(-chunk // st.cycle) * st.cycle, cap // st.cycle * st.cycle
         st.prepare(max(1, min(chunk, cap)))
         st.synchronize()
         ctx.barrier()
@@ -756,6 +838,9 @@ def main(argv=None) -> int:
            "fixed_edges": st.fixed_edge_note(), "halo_mode": st.halo_mode(),
            "evaluation": ("scaled form" if st.scaled_form_active else "sum form" if st.sum_form_active
                           else "per step")}
+    info = st.relaxation_info()
+    rec.update(relaxation=cfg.relaxation, cycle=info["cycle"], omega_min=info["omega_min"], omega_max=info["omega_max"],
+               cycle_growth=info["growth"], relaxation_note=st.relaxation_note())
     if until is not None:
         rec.update(converged=until["converged"], iterations=until["iterations"], residual=until["residual"],
                    checks=until["checks"], norm=until["norm"], reason=until["reason"], tol=args.tol,
