@@ -39,6 +39,9 @@
 // --relaxation chebyshev (with --non-periodic --block-fixed-edges on a solver backend: every time block is one
 // Chebyshev cycle, kernels/relaxation.hpp; --iters and --check-every in whole cycles, the field is meaningful
 // at cycle ends only; default time block 24 fp32 / 16 fp64),
+// --source Q (a constant source term g = Q in every cell, u' = A u + g: implies --non-periodic and
+// --block-fixed-edges, needs a solver backend and a time block with level kernels, fp32 20 / 24, fp64 12 / 16,
+// the default; --iters, --warmup and --check-every in whole cycles; the residual is A u + g - u),
 // --tol T [--check-every N] (iterate until the linf residual A u - u is <= T, checked every N iterations,
 // default 16 time blocks, with --iters as the cap; prints "converged after K iterations, residual R (linf)"),
 // --checkpoint FILE / --resume FILE (collective MPI-IO global grid file, any
@@ -102,7 +105,8 @@ int run(MpiEnv& env, const Cli& cli, const CartTopology& topo, const DeviceBindi
   // A non-periodic grid has fixed boundary values that the S-step kernels
   // would advance as cells: one exchange per iteration there (as the solver
   // does), unless --block-fixed-edges hands the frame to the held-side kernel.
-  const bool block_fixed = cli.flag("block-fixed-edges");
+  const bool source = cli.has("source");
+  const bool block_fixed = cli.flag("block-fixed-edges") || source;
   const bool all_periodic = (topo.periodic_rows && topo.periodic_cols) || block_fixed;
   const double c_center = cli.get_double("c-center", 0.2), c_neighbor = cli.get_double("c-neighbor", 0.2);
   // --no-sum-form: per-step evaluation everywhere (bitwise equal to the CPU app).
@@ -111,10 +115,13 @@ int run(MpiEnv& env, const Cli& cli, const CartTopology& topo, const DeviceBindi
   MXS_CHECK(relaxation == "none" || relaxation == "chebyshev", "--relaxation must be none or chebyshev, got " << relaxation);
   const bool chebyshev = relaxation == "chebyshev";
   MXS_CHECK(!chebyshev || backend != "mpi-staged", "--relaxation chebyshev runs on the solver backends");
+  MXS_CHECK(!source || backend != "mpi-staged", "--source runs on the solver backends");
+  MXS_CHECK(!source || iters > 0, "--source needs a timed run (--iters > 0)");
+  const bool cycles = chebyshev || source;  // the cycle is the unit of progress
   int time_block =
       (backend == "mpi-staged" || !all_periodic)
           ? 1
-          : int(cli.get_int("time-block", chebyshev ? kernels::relaxation_auto_depth(int(sizeof(T)), lw, lh)
+          : int(cli.get_int("time-block", cycles ? kernels::relaxation_auto_depth(int(sizeof(T)), lw, lh)
                                           : iters > 0 && lw >= 64 && lh >= 64
                                               ? kernels::auto_time_block(lw, lh, int(sizeof(T)), sum_form)
                                               : 1));
@@ -168,6 +175,7 @@ int run(MpiEnv& env, const Cli& cli, const CartTopology& topo, const DeviceBindi
   cfg.time_block = time_block;
   cfg.block_fixed_edges = block_fixed;
   cfg.relaxation = chebyshev ? Relaxation::Chebyshev : Relaxation::None;
+  cfg.source = source;
   cfg.global_width = gw;
   cfg.global_height = gh;
   std::unique_ptr<StencilSolver<T>> solver;
@@ -303,7 +311,14 @@ int run(MpiEnv& env, const Cli& cli, const CartTopology& topo, const DeviceBindi
       }
     };
     long long warmup = cli.get_int("warmup", 10);
-    if (chebyshev && solver) warmup = (warmup + solver->time_block() - 1) / solver->time_block() * solver->time_block();  // whole cycles
+    if (source) {  // g = Q on the core of a tile of the solver's geometry; the solver keeps its own copy
+      DeviceBuffer<T> gt(g.alloc_elems());
+      kernels::fill<T>(gt.get(), g.alloc_elems(), T(0), init_stream.get());
+      kernels::fill_region<T>(gt.get(), g.core(), T(cli.get_double("source", 0.0)), init_stream.get());
+      init_stream.sync();
+      solver->set_source(gt.get());
+    }
+    if (cycles && solver) warmup = (warmup + solver->time_block() - 1) / solver->time_block() * solver->time_block();  // whole cycles
     steps(warmup);
     if (solver && !fault.armed()) {  // graphs + first launches, untimed
       const long long chunk = check_every > 0 ? check_every : (long long)kDefaultCheckBlocks * solver->time_block();
@@ -355,6 +370,8 @@ int run(MpiEnv& env, const Cli& cli, const CartTopology& topo, const DeviceBindi
         js << ", \"relaxation\": \"" << relaxation << "\", \"cycle\": " << solver->relaxation_cycle()
            << ", \"omega_min\": " << solver->relaxation_omega_min() << ", \"omega_max\": " << solver->relaxation_omega_max()
            << ", \"cycle_growth\": " << solver->relaxation_growth();
+        if (source) js << ", \"source\": " << cli.get_double("source", 0.0);
+        else js << ", \"source\": null";
       }
       if (until)
         js << ", \"tol\": " << app::fmt(tol) << ", \"converged\": " << (conv.converged ? "true" : "false")
@@ -411,7 +428,7 @@ int main(int argc, char** argv) {
     if (env.rank() == 0) std::cerr << "process grid " << rows << "x" << cols << " != " << n << " ranks" << std::endl;
     return 1;
   }
-  const bool periodic = !cli.flag("non-periodic");
+  const bool periodic = !cli.flag("non-periodic") && !cli.has("source");  // a source term implies fixed edges
   const CartTopology topo(rows, cols, periodic, periodic);
   const auto c = topo.coords(env.rank());
   const auto& pos = cli.positional();

@@ -10,6 +10,8 @@
 //   K2/4/5/8 dot_atomic, dot_partials, reduce_partials, dot_single_pass, dot_racy
 //                                                kernels/dot.hip
 //          stencil5_residual (norms of A u - u)  kernels/residual.hip
+//   K13    level passes with a correction tile, source_axpy (the source term)
+//                                                kernels/stencil_pipe_levels_src_f32/_f64.hip, stencil_levels_src.hip
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -246,6 +248,25 @@ void stencil5_tb_levels(const T* in, T* out, const TileGeom& g, index_t x0, inde
 template <typename T>
 void stencil5_tb_held_levels(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1,
                              const LevelTable& t, unsigned hold, hipStream_t s);
+// The same passes with a correction tile (the source term, docs/ARCHITECTURE.md
+// "Source term"): `corr` is a tile of geometry g, and the pass ends with
+// out += corr on the rectangle, one rounded add per cell, inside the same
+// launch ("stream_pipe_levels_src" / "held_levels_src"): bitwise the pass
+// without corr followed by that add. Only the rectangle's cells of corr are
+// read, so its ghost ring and padding may hold anything. corr == nullptr runs
+// exactly the launch above. Kernels: stencil_pipe_levels_src_f32/_f64.hip,
+// stencil_levels_src.hip.
+template <typename T>
+void stencil5_tb_levels(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1,
+                        const LevelTable& t, const T* corr, hipStream_t s);
+template <typename T>
+void stencil5_tb_held_levels(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1,
+                             const LevelTable& t, unsigned hold, const T* corr, hipStream_t s);
+// The build step of the correction: tile core += T(w) * src core with fixed
+// rounding points (the product rounded, then the sum; never an fma), so it
+// equals a rounded multiply and a rounded add of any other implementation.
+template <typename T>
+void source_axpy(T* tile, const T* src, const TileGeom& g, double w, hipStream_t s);
 
 // ------------------------------------- chunk-list pass (interior-first super-step)
 // The S-step pass over chunks of the core of a ghost-ring tile (no wrap) on the
@@ -304,7 +325,10 @@ struct ResidualNorms {  // device layout: what the kernel leaves in *out
 int residual_grid_size(const TileGeom& g);
 template <typename T>
 void stencil5_residual(const T* u, const TileGeom& g, Stencil5Coeffs c, ResidualNorms* out, double* partials,
-                       unsigned* counter, hipStream_t s);
+                       unsigned* counter, hipStream_t s, const T* src = nullptr);
+// src: a tile of geometry g whose core holds the additive term g of
+// u' = A u + g; the residual is then r = (fma(...) + g) - v, each one rounded
+// operation. Only core cells of src are read. Same grid, determinism and finish.
 
 // Whether work on stream b runs while a kernel on stream a still runs (the two
 // sit on different hardware queues): one bounded ~0.8 ms sleeping wave on a, a

@@ -245,6 +245,18 @@ struct SolverConfig {
   // cycle ends (inside a cycle it strays by up to growth x max|u|).
   Relaxation relaxation = Relaxation::None;
   index_t global_width = 0, global_height = 0;  // the global core (Chebyshev: the spectrum's bounds)
+  // This solver takes a source term: u' = A u + g (set_source). One cycle with
+  // a source is the homogeneous level-table pass plus a correction G added
+  // where the pass stores, G built once per set_source from g and the table
+  // (docs/ARCHITECTURE.md "Source term"). Needs what the Chebyshev mode needs:
+  // Jacobi5, a topology non-periodic in both axes, block_fixed_edges, the
+  // global grid size and a time block with level kernels (time_block <= 0 picks
+  // it the same way); otherwise the constructor throws, naming the missing
+  // condition. With relaxation = None the passes run a uniform level table of
+  // time_block levels (plain Jacobi, bitwise the per-step pass). Either way the
+  // passes take the per-step form, the cycle is the unit of progress (run(K)
+  // needs K % M == 0) and the field is the iterate at cycle ends only.
+  bool source = false;
   StencilKind kind = StencilKind::Jacobi5;
   kernels::Stencil5Coeffs coeffs;
   kernels::BoxWeights box;
@@ -368,6 +380,20 @@ class StencilSolver {
     ghost_fresh_ = false;
     range_checked_ = false;
   }
+  // Collective (SolverConfig::source): g_tile is a device tile of the solver's
+  // geometry whose core holds g, the additive term of one base Jacobi step
+  // u' = A u + g; nullptr clears the source. The solver keeps its own copies: g
+  // and the cycle's correction G, built here by G_0 = 0, G_{l+1} = C_l G_l +
+  // w_l g (M single steps on a tile whose ring is 0 on physical sides, each
+  // behind a halo exchange of the backend, then kernels::source_axpy), and
+  // throws if G is not finite. From then on every cycle adds G where it stores
+  // and residual() is r = A u + g - u. Drops the captured graphs (the kernel
+  // arguments change) and ends like field_changed(). Until it is called the
+  // solver runs the homogeneous level passes.
+  void set_source(const T* g_tile);
+  bool source_set() const { return src_set_; }
+  // The correction tile G (nullptr while no source is set).
+  const T* source_correction() const { return src_set_ ? src_G_.get() : nullptr; }
   // Fault injection (like the apps' --fault-inject): the host
   // sleeps `seconds` on entering `phase` ("prepare", "warm", "run",
   // "profile_window"), so tests can stall one rank inside a collective phase
@@ -451,7 +477,8 @@ class StencilSolver {
   bool scaled_form_active() const { return kernels::requested_form(cfg_.coeffs) == kernels::EvalForm::Scaled; }
   // Why the sum form is off when the coefficients are equal ("" when on).
   const std::string& sum_form_note() const { return sum_note_; }
-  // Relaxation cycle ("" / 0 with Relaxation::None): which passes run and why
+  // Relaxation cycle ("" / 0 without a level-table cycle; SolverConfig::source
+  // without Chebyshev runs a uniform table): which passes run and why
   // (the level passes, or the plain per-step pass when the range guard
   // growth x max|u| < max(T) / 4 fails), with M, the weights' range and growth.
   std::string relaxation_note() const;
@@ -637,8 +664,14 @@ class StencilSolver {
   double local_absmax_ = 0;
   // Chebyshev relaxation: the agreed level table (rank 0's bits on every rank)
   // and whether the passes run it (the range guard, ensure_range()).
-  bool relax_ = false;
+  bool relax_ = false;                       // a level-table cycle: Chebyshev, or a source's uniform table
+  bool cheb_ = false;                        // the table is a Chebyshev cycle
   bool relax_on_ = false;
+  // Source term (SolverConfig::source): the solver's copies of g and of the
+  // cycle's correction G, and the levels' weights the build uses.
+  bool src_set_ = false;
+  DeviceBuffer<T> src_g_, src_G_;
+  double omega_[kernels::kMaxLevels] = {};
   kernels::LevelTable levels_;
   double omega_min_ = 0, omega_max_ = 0;
   std::string relax_guard_;                  // why the plain pass runs ("" when the level passes do)

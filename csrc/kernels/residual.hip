@@ -27,6 +27,9 @@
 //     size works;
 //   * rows are dealt to workgroups in contiguous bands (a multiple of kCh
 //     rows): the only re-read is one row above and below each band.
+// With a source tile g (u' = A u + g) the residual is r = (A u + g) - u: the
+// stencil expression, then + g, then - v, each one rounded operation; g is read
+// on core cells only.
 // Deterministic: per-workgroup partials and a last-block finish in a fixed
 // order (the dot_single_pass recipe of dot.hip: agent-scope release before the
 // ticket, acquire after); no floating-point atomics. The grid depends only on
@@ -125,12 +128,16 @@ __device__ __forceinline__ Pair block_reduce(Pair v, unsigned long long* lds) {
 
 // Grid: gx column groups (kResWaves strips each) x bands of band_rows rows,
 // workgroup b = band * gx + group. partials: 2 doubles per workgroup.
-template <typename T>
+// SRC: r = (A u + g) - u with g the core of the tile `gsrc` (same geometry),
+// loaded beside each centre row at the centre row's own offsets and only where
+// the centre vector holds core cells.
+template <typename T, bool SRC>
 __global__ __launch_bounds__(kResBlock) void stencil5_residual_kernel(const T* __restrict__ u, index_t pitch,
                                                                       index_t core_off, index_t W, index_t H,
                                                                       unsigned gx, index_t band_rows, T c0, T c1,
                                                                       int vec_ok, ResidualNorms* out,
-                                                                      double* partials, unsigned* counter) {
+                                                                      double* partials, unsigned* counter,
+                                                                      const T* __restrict__ gsrc) {
   constexpr int N = ResVec<T>::N;
   constexpr index_t SEG = index_t(kWaveSize) * N;
   using V = typename ResVec<T>::type;
@@ -188,6 +195,22 @@ __global__ __launch_bounds__(kResBlock) void stencil5_residual_kernel(const T* _
       return v;
     }
   };
+  // Row y (a core row) of the source tile: whole vectors of core cells, or the
+  // ragged vector's core cells one by one.
+  auto ldg = [&](auto fast_tag, index_t y) -> V {
+    V v = V(T(0));
+    if constexpr (SRC) {
+      if constexpr (decltype(fast_tag)::value) {
+        v = __builtin_nontemporal_load(reinterpret_cast<const V*>(gsrc + (pf - u) + y * pitch));
+      } else {
+        const T* __restrict__ q = gsrc + core_off + x + y * pitch;
+#pragma unroll
+        for (int i = 0; i < N; ++i)
+          if (i < nvalid) v[i] = q[i];
+      }
+    }
+    return v;
+  };
   struct Edge {
     T l, r;
   };
@@ -205,7 +228,7 @@ __global__ __launch_bounds__(kResBlock) void stencil5_residual_kernel(const T* _
 
   U m = 0;
   double acc = 0.0;
-  auto emit = [&](const V& up, const V& mid, const V& dn, Edge e) {
+  auto emit = [&](const V& up, const V& mid, const V& dn, Edge e, const V& gv) {
     T left = lane_shift<kDppWaveShr1>(mid[N - 1]);  // lane i - 1's last element
     T right = lane_shift<kDppWaveShl1>(mid[0]);      // lane i + 1's first
     left = lane == 0 ? e.l : left;
@@ -214,7 +237,9 @@ __global__ __launch_bounds__(kResBlock) void stencil5_residual_kernel(const T* _
     for (int i = 0; i < N; ++i) {
       const T w = i == 0 ? left : mid[i > 0 ? i - 1 : 0];
       const T ea = i == N - 1 ? right : mid[i < N - 1 ? i + 1 : 0];
-      T r = fma_t<T>(c1, (up[i] + dn[i]) + (w + ea), c0 * mid[i]) - mid[i];
+      T r = fma_t<T>(c1, (up[i] + dn[i]) + (w + ea), c0 * mid[i]);
+      if constexpr (SRC) r = r + gv[i];
+      r = r - mid[i];
       r = i < nvalid ? r : T(0);  // a select: whatever sits past the core never enters
       m = umax<U>(m, abs_bits(r));
       acc = __builtin_fma(double(r), double(r), acc);
@@ -228,6 +253,7 @@ __global__ __launch_bounds__(kResBlock) void stencil5_residual_kernel(const T* _
   struct Chunk {
     V v[kCh];
     Edge e[kCh];
+    V g[SRC ? kCh : 1];  // the source beside the rows that become a centre row
   };
   auto walk = [&](auto fast_tag) {
     auto load = [&](index_t y, bool guarded) -> Chunk {
@@ -239,12 +265,17 @@ __global__ __launch_bounds__(kResBlock) void stencil5_residual_kernel(const T* _
         c.e[k] = Edge{T(0), T(0)};
         if (!guarded || yn <= y1) c.v[k] = ldv(fast_tag, yn, yn < H);
         if (!guarded || yn < y1) c.e[k] = lde(fast_tag, yn);
+        if constexpr (SRC) {
+          c.g[k] = V(T(0));
+          if (!guarded || yn < y1) c.g[k] = ldg(fast_tag, yn);
+        }
       }
       return c;
     };
     V up = ldv(fast_tag, y0 - 1, y0 > 0);
     V mid = ldv(fast_tag, y0, true);
     Edge emid = lde(fast_tag, y0);
+    V gmid = ldg(fast_tag, y0);
     index_t y = y0;
     Chunk cur = load(y, true);
 #pragma unroll 1
@@ -252,10 +283,11 @@ __global__ __launch_bounds__(kResBlock) void stencil5_residual_kernel(const T* _
       const Chunk nxt = load(y + kCh, false);
 #pragma unroll
       for (int k = 0; k < kCh; ++k) {
-        emit(up, mid, cur.v[k], emid);
+        emit(up, mid, cur.v[k], emid, gmid);
         up = mid;
         mid = cur.v[k];
         emid = cur.e[k];
+        if constexpr (SRC) gmid = cur.g[k];
       }
       cur = nxt;
     }
@@ -265,10 +297,11 @@ __global__ __launch_bounds__(kResBlock) void stencil5_residual_kernel(const T* _
       if (y + kCh < y1) nxt = load(y + kCh, true);
 #pragma unroll
       for (int k = 0; k < kCh; ++k) {
-        if (y + k < y1) emit(up, mid, cur.v[k], emid);
+        if (y + k < y1) emit(up, mid, cur.v[k], emid, gmid);
         up = mid;
         mid = cur.v[k];
         emid = cur.e[k];
+        if constexpr (SRC) gmid = cur.g[k];
       }
       cur = nxt;
     }
@@ -339,7 +372,7 @@ int residual_grid_size(const TileGeom& g) {
 
 template <typename T>
 void stencil5_residual(const T* u, const TileGeom& g, Stencil5Coeffs c, ResidualNorms* out, double* partials,
-                       unsigned* counter, hipStream_t s) {
+                       unsigned* counter, hipStream_t s, const T* src) {
   MXS_CHECK(g.halo_x >= 1 && g.halo_y >= 1,
             "stencil5_residual: the tile has no ghost ring (it needs one at least 1 deep)");
   MXS_CHECK(g.width >= 0 && g.height >= 0 && g.pitch >= g.x_origin + g.total_width(),
@@ -357,19 +390,26 @@ void stencil5_residual(const T* u, const TileGeom& g, Stencil5Coeffs c, Residual
   const ResGrid rg = residual_grid(g, int(sizeof(T)));
   const index_t grid = index_t(rg.gx) * rg.bands;
   MXS_CHECK(grid <= index_t(residual_grid_size(g)) && grid < (index_t(1) << 31), "stencil5_residual: grid size");
-  const int vec_ok = reinterpret_cast<std::uintptr_t>(u + g.core_offset()) % 16 == 0 && g.pitch % N == 0;
+  const int vec_ok = reinterpret_cast<std::uintptr_t>(u + g.core_offset()) % 16 == 0 && g.pitch % N == 0 &&
+                     (src == nullptr || reinterpret_cast<std::uintptr_t>(src + g.core_offset()) % 16 == 0);
+  MXS_CHECK(reinterpret_cast<std::uintptr_t>(src) % sizeof(T) == 0, "stencil5_residual: pointers must be element-aligned");
   // Re-initialise the ticket every call (a memset node under graph capture).
   MXS_HIP_CHECK(hipMemsetAsync(counter, 0, sizeof(unsigned), s));
-  stencil5_residual_kernel<T><<<unsigned(grid), kResBlock, 0, s>>>(u, g.pitch, g.core_offset(), g.width, g.height,
-                                                                    rg.gx, rg.band_rows, T(c.center), T(c.neighbor),
-                                                                    vec_ok, out, partials, counter);
+  if (src)
+    stencil5_residual_kernel<T, true><<<unsigned(grid), kResBlock, 0, s>>>(
+        u, g.pitch, g.core_offset(), g.width, g.height, rg.gx, rg.band_rows, T(c.center), T(c.neighbor), vec_ok, out,
+        partials, counter, src);
+  else
+    stencil5_residual_kernel<T, false><<<unsigned(grid), kResBlock, 0, s>>>(
+        u, g.pitch, g.core_offset(), g.width, g.height, rg.gx, rg.band_rows, T(c.center), T(c.neighbor), vec_ok, out,
+        partials, counter, nullptr);
   MXS_HIP_CHECK_LAUNCH();
 }
 
 template void stencil5_residual<float>(const float*, const TileGeom&, Stencil5Coeffs, ResidualNorms*, double*,
-                                       unsigned*, hipStream_t);
+                                       unsigned*, hipStream_t, const float*);
 template void stencil5_residual<double>(const double*, const TileGeom&, Stencil5Coeffs, ResidualNorms*, double*,
-                                        unsigned*, hipStream_t);
+                                        unsigned*, hipStream_t, const double*);
 
 }  // namespace kernels
 }  // namespace mxs

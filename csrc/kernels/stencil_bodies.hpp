@@ -63,6 +63,35 @@ template <typename T, int S>
 __device__ __forceinline__ CoeffPair<T> level_coeff(const LevelPairs<T, S>& c, int l) {
   return c.v[l];
 }
+// A level source may also carry a correction tile that the pipeline adds to
+// every stored cell (the source term, stencil_pipe_levels_src.hpp). The
+// pipeline asks CoeffCorr<C>::value at compile time, so the kernels of every
+// other coefficient source keep their instructions.
+template <typename C>
+struct CoeffCorr {
+  static constexpr bool value = false;
+};
+template <typename T, int S>
+struct LevelPairsSrc {
+  LevelPairs<T, S> pairs;
+  const T* corr;  // a tile of the pass's geometry; only core cells are read
+};
+template <typename T, int S>
+struct CoeffCorr<LevelPairsSrc<T, S>> {
+  static constexpr bool value = true;
+};
+template <typename T, int S>
+__device__ __forceinline__ CoeffPair<T> level_coeff(const LevelPairsSrc<T, S>& c, int l) {
+  return c.pairs.v[l];
+}
+template <typename C>
+__device__ __forceinline__ const void* coeff_corr(const C&) {
+  return nullptr;
+}
+template <typename T, int S>
+__device__ __forceinline__ const T* coeff_corr(const LevelPairsSrc<T, S>& c) {
+  return c.corr;
+}
 
 constexpr int kWavesPerBlock = 4;
 constexpr int kNumXcds = 8;  // MI355X: workgroups are dealt round-robin over 8 XCDs
@@ -292,6 +321,34 @@ struct BodyWideF64 {  // 4 consecutive fp64 cells per lane (jac_w4d)
     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), r, int(off + 16u), 0, 2 /* nt */);
   }
 };
+
+// A lane's 4 cells of a correction tile (CoeffCorr), loaded through a buffer
+// descriptor laid over it like the output's and at the store's own offset: a
+// dropped lane or row is past the range and loads 0. The add is one rounded
+// operation per cell, in natural cell order (after rot_out for the rotated
+// fp32 layout), then the store of the body.
+template <typename T>
+struct CorrRow {
+  u32x4 v[sizeof(T) / 4];
+};
+__device__ __forceinline__ void corr_load(CorrRow<float>& c, __amdgpu_buffer_rsrc_t r, unsigned off) {
+  c.v[0] = __builtin_amdgcn_raw_buffer_load_b128(r, int(off), 0, 0);
+}
+__device__ __forceinline__ void corr_load(CorrRow<double>& c, __amdgpu_buffer_rsrc_t r, unsigned off) {
+  c.v[0] = __builtin_amdgcn_raw_buffer_load_b128(r, int(off), 0, 0);
+  c.v[1] = __builtin_amdgcn_raw_buffer_load_b128(r, int(off + 16u), 0, 0);
+}
+__device__ __forceinline__ void corr_store(const f32x4& top, const CorrRow<float>& c, __amdgpu_buffer_rsrc_t r,
+                                           unsigned off) {
+  const f32x4 nat = rot_out(top) + __builtin_bit_cast(f32x4, c.v[0]);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, nat), r, int(off), 0, 2 /* nt */);
+}
+__device__ __forceinline__ void corr_store(const f64x4& top, const CorrRow<double>& c, __amdgpu_buffer_rsrc_t r,
+                                           unsigned off) {
+  const f64x2 lo = top.xy + __builtin_bit_cast(f64x2, c.v[0]), hi = top.zw + __builtin_bit_cast(f64x2, c.v[1]);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, lo), r, int(off), 0, 2 /* nt */);
+  __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), r, int(off + 16u), 0, 2 /* nt */);
+}
 
 // Sum form (c_center == c_neighbor == c, the default 5-point average). The
 // S-level recurrence u' = c * (5-point sum of u) is linear with one uniform

@@ -89,7 +89,10 @@ struct PipeShape {
 // hands level l of the pass, counted over both stages, its own pair. The level
 // index is a constant in every unrolled level loop below, and with C = B::T the
 // kernels compile to the instructions they had before the parameter existed
-// (scripts/isa_same.py).
+// (scripts/isa_same.py). A source that carries a correction tile (CoeffCorr,
+// stencil_bodies.hpp: the source term) makes stage 1 load the tile's cells at
+// the store's offsets and add them to the row it stores; every other source
+// compiles as before.
 struct BlockStamps {
   unsigned long long parked = 0, body = 0;
 };
@@ -294,6 +297,10 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
     // Output descriptor over rows [ys, ye) (see stream_chunk_fast).
     const index_t x0w = gx - index_t(lane) * N;  // the window's first column
     const __amdgpu_buffer_rsrc_t orsrc = chunk_out_rsrc(out + core_off + x0w + ys * pitch, rows, pitch);
+    // A correction tile (CoeffCorr): the same descriptor over it, read at the store's offsets.
+    constexpr bool CORR = CoeffCorr<C>::value;
+    __amdgpu_buffer_rsrc_t crsrc;
+    if constexpr (CORR) crsrc = chunk_out_rsrc(coeff_corr(c0) + core_off + x0w + ys * pitch, rows, pitch);
     bool store_lane;
     if constexpr (JOINT) {
       // Inside this window's own apron and inside the group's output span
@@ -364,6 +371,12 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
         block_prio_row<BPRIO, 1>(k);
         const index_t j = i + k;
         V top;
+        // The row's correction first: its latency falls behind the S1 levels.
+        CorrRow<T> cv;
+        if constexpr (CORR) {
+          const int rc = int(j - E1);
+          corr_load(cv, crsrc, lane_term + (rc >= 0 && rc < rows_i ? unsigned(rc) * row_bytes : unsigned(kMaxChunkBytes)));
+        }
         if constexpr (ASC1) {
           const int n = k % 3, o = (k + 1) % 3, m = (k + 2) % 3;
           win[n][0] = inrow[k];
@@ -385,7 +398,8 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
         }
         const int r = int(j - E1);
         const unsigned row_term = r >= 0 && r < rows_i ? unsigned(r) * row_bytes : unsigned(kMaxChunkBytes);
-        B::store(top, orsrc, lane_term + row_term, level_coeff(c0, 0));
+        if constexpr (CORR) corr_store(top, cv, orsrc, lane_term + row_term);
+        else B::store(top, orsrc, lane_term + row_term, level_coeff(c0, 0));
       }
       block_barrier<STAMP>(stamps, released);
     }

@@ -13,6 +13,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 #include "mxs/comm/rccl_comm.hpp"
 #include "mxs/core/fault.hpp"
@@ -223,25 +224,29 @@ PYBIND11_MODULE(_mxs_hip, m) {
       py::arg("x"), py::arg("n"), py::arg("dtype") = "f32", "max |x[i]| (device reduction; NaN if any is NaN)");
   m.def(
       "stencil5_residual",
-      [](std::uintptr_t x, const TileGeom& g, double c0, double c1, const std::string& dt, std::uintptr_t s) {
+      [](std::uintptr_t x, const TileGeom& g, double c0, double c1, const std::string& dt, std::uintptr_t s,
+         std::uintptr_t source) {
         kernels::Stencil5Coeffs c{c0, c1};
         const index_t grid = kernels::residual_grid_size(g);
         DeviceBuffer<double> buf(2 + 2 * grid);
         DeviceBuffer<unsigned> counter(1);
         auto* norms = reinterpret_cast<kernels::ResidualNorms*>(buf.get());
         if (parse_dtype(dt) == DType::F32)
-          kernels::stencil5_residual<float>(ptr<float>(x), g, c, norms, buf.get() + 2, counter.get(), strm(s));
+          kernels::stencil5_residual<float>(ptr<float>(x), g, c, norms, buf.get() + 2, counter.get(), strm(s),
+                                            ptr<float>(source));
         else
-          kernels::stencil5_residual<double>(ptr<double>(x), g, c, norms, buf.get() + 2, counter.get(), strm(s));
+          kernels::stencil5_residual<double>(ptr<double>(x), g, c, norms, buf.get() + 2, counter.get(), strm(s),
+                                             ptr<double>(source));
         kernels::ResidualNorms h{0.0, 0.0};
         MXS_HIP_CHECK(hipMemcpyAsync(&h, norms, sizeof(h), hipMemcpyDeviceToHost, strm(s)));
         MXS_HIP_CHECK(hipStreamSynchronize(strm(s)));
         return py::make_tuple(h.linf, h.sumsq);
       },
       py::arg("src"), py::arg("geom"), py::arg("c_center") = 0.2, py::arg("c_neighbor") = 0.2,
-      py::arg("dtype") = "f32", py::arg("stream") = 0,
+      py::arg("dtype") = "f32", py::arg("stream") = 0, py::arg("source") = 0,
       "(max |r|, sum r^2) of the Jacobi residual r = A u - u over the core of a ghost-ring tile "
-      "(reads the core and the ring cells beside it only; synchronises the stream)");
+      "(reads the core and the ring cells beside it only; synchronises the stream); source: a tile of the same "
+      "geometry whose core holds g, then r = A u + g - u (0: none)");
   m.def(
       "residual_kernel_times",
       [](std::uintptr_t x, const TileGeom& g, double c0, double c1, const std::string& dt, int reps) {
@@ -386,33 +391,45 @@ PYBIND11_MODULE(_mxs_hip, m) {
       "stencil5_tb_levels",
       [level_table](std::uintptr_t in, std::uintptr_t out, const TileGeom& g, index_t x0, index_t x1, index_t y0,
                     index_t y1, const std::vector<double>& center, const std::vector<double>& neighbor,
-                    const std::string& dt, std::uintptr_t s) {
+                    const std::string& dt, std::uintptr_t s, std::uintptr_t corr) {
         const kernels::LevelTable t = level_table(center, neighbor);
         if (parse_dtype(dt) == DType::F32)
-          kernels::stencil5_tb_levels<float>(ptr<float>(in), ptr<float>(out), g, x0, x1, y0, y1, t, strm(s));
+          kernels::stencil5_tb_levels<float>(ptr<float>(in), ptr<float>(out), g, x0, x1, y0, y1, t, ptr<float>(corr),
+                                             strm(s));
         else
-          kernels::stencil5_tb_levels<double>(ptr<double>(in), ptr<double>(out), g, x0, x1, y0, y1, t, strm(s));
+          kernels::stencil5_tb_levels<double>(ptr<double>(in), ptr<double>(out), g, x0, x1, y0, y1, t,
+                                              ptr<double>(corr), strm(s));
       },
       py::arg("src"), py::arg("dst"), py::arg("geom"), py::arg("x0"), py::arg("x1"), py::arg("y0"), py::arg("y1"),
-      py::arg("center"), py::arg("neighbor"), py::arg("dtype") = "f32", py::arg("stream") = 0,
+      py::arg("center"), py::arg("neighbor"), py::arg("dtype") = "f32", py::arg("stream") = 0, py::arg("corr") = 0,
       "one pass of len(center) levels over [x0, x1) x [y0, y1) of a ghost-ring tile, level l with (center[l], "
       "neighbor[l]): the per-step stencil5_tb (no wrap) with a level table; fp32 20 / 24 levels, fp64 12 / 16");
   m.def(
       "stencil5_tb_held_levels",
       [level_table](std::uintptr_t in, std::uintptr_t out, const TileGeom& g, index_t x0, index_t x1, index_t y0,
                     index_t y1, const std::vector<double>& center, const std::vector<double>& neighbor, unsigned hold,
-                    const std::string& dt, std::uintptr_t s) {
+                    const std::string& dt, std::uintptr_t s, std::uintptr_t corr) {
         const kernels::LevelTable t = level_table(center, neighbor);
         if (parse_dtype(dt) == DType::F32)
-          kernels::stencil5_tb_held_levels<float>(ptr<float>(in), ptr<float>(out), g, x0, x1, y0, y1, t, hold, strm(s));
+          kernels::stencil5_tb_held_levels<float>(ptr<float>(in), ptr<float>(out), g, x0, x1, y0, y1, t, hold,
+                                                  ptr<float>(corr), strm(s));
         else
           kernels::stencil5_tb_held_levels<double>(ptr<double>(in), ptr<double>(out), g, x0, x1, y0, y1, t, hold,
-                                                   strm(s));
+                                                   ptr<double>(corr), strm(s));
       },
       py::arg("src"), py::arg("dst"), py::arg("geom"), py::arg("x0"), py::arg("x1"), py::arg("y0"), py::arg("y1"),
       py::arg("center"), py::arg("neighbor"), py::arg("hold") = 15u, py::arg("dtype") = "f32", py::arg("stream") = 0,
+      py::arg("corr") = 0,
       "stencil5_tb_held with a level table: level l runs (center[l], neighbor[l]); cells outside the core on a held "
       "side keep their input value at every level");
+  m.def(
+      "source_axpy",
+      [](std::uintptr_t tile, std::uintptr_t src, const TileGeom& g, double w, const std::string& dt, std::uintptr_t s) {
+        if (parse_dtype(dt) == DType::F32) kernels::source_axpy<float>(ptr<float>(tile), ptr<float>(src), g, w, strm(s));
+        else kernels::source_axpy<double>(ptr<double>(tile), ptr<double>(src), g, w, strm(s));
+      },
+      py::arg("tile"), py::arg("src"), py::arg("geom"), py::arg("w"), py::arg("dtype") = "f32", py::arg("stream") = 0,
+      "tile core += T(w) * src core: the product rounded, then the sum (the build step of a source's correction)");
   m.attr("HOLD_TOP") = unsigned(kernels::kHoldTop);
   m.attr("HOLD_BOTTOM") = unsigned(kernels::kHoldBottom);
   m.attr("HOLD_LEFT") = unsigned(kernels::kHoldLeft);
@@ -606,8 +623,9 @@ PYBIND11_MODULE(_mxs_hip, m) {
                        double min_gain, int halo_max_ctas, int main_priority, int side_priority,
                        double wire_delay_us, const std::string& direct_engine, const std::string& steady,
                        bool block_fixed_edges, const std::string& relaxation, index_t global_width,
-                       index_t global_height) {
+                       index_t global_height, bool source) {
              SolverConfig cfg;
+             cfg.source = source;
              cfg.block_fixed_edges = block_fixed_edges;
              if (relaxation == "none") cfg.relaxation = Relaxation::None;
              else if (relaxation == "chebyshev") cfg.relaxation = Relaxation::Chebyshev;
@@ -662,7 +680,37 @@ PYBIND11_MODULE(_mxs_hip, m) {
            py::arg("min_gain") = 0.0, py::arg("halo_max_ctas") = 0, py::arg("main_priority") = -1,
            py::arg("side_priority") = 0, py::arg("wire_delay_us") = 0.0, py::arg("direct_engine") = "kernel",
            py::arg("steady") = "auto", py::arg("block_fixed_edges") = false, py::arg("relaxation") = "none",
-           py::arg("global_width") = 0, py::arg("global_height") = 0, py::keep_alive<1, 7>())
+           py::arg("global_width") = 0, py::arg("global_height") = 0, py::arg("source") = false,
+           py::keep_alive<1, 7>())
+      .def(
+          "set_source",
+          [](SolverHandle& h, std::uintptr_t g_tile) {
+            if (h.dt == DType::F32) h.f->set_source(ptr<float>(g_tile));
+            else h.d->set_source(ptr<double>(g_tile));
+          },
+          py::arg("g_tile"), py::call_guard<py::gil_scoped_release>(),
+          "collective: take the source term from a device tile of the solver's geometry whose core holds g "
+          "(u' = A u + g); 0 clears it. Builds the cycle's correction, drops captured graphs, ends like field_changed()")
+      .def(
+          "source_correction",
+          [](SolverHandle& h) {
+            return h.visit([](auto& s) { return reinterpret_cast<std::uintptr_t>(s.source_correction()); });
+          },
+          "device address of the cycle's correction tile G (0 while no source is set)")
+      .def(
+          "copy_source_correction",
+          [](SolverHandle& h, std::uintptr_t dst) {
+            return h.visit([dst](auto& s) {
+              if (!s.source_correction()) return false;
+              s.synchronize();
+              using E = std::remove_const_t<std::remove_pointer_t<decltype(s.source_correction())>>;
+              MXS_HIP_CHECK(hipMemcpy(reinterpret_cast<void*>(dst), s.source_correction(),
+                                      size_t(s.plan().tile.alloc_elems()) * sizeof(E), hipMemcpyDeviceToDevice));
+              return true;
+            });
+          },
+          py::arg("dst"), "copy the correction tile G into a device tile of the solver's geometry (false: no source set)")
+      .def("source_set", [](SolverHandle& h) { return h.visit([](auto& s) { return s.source_set(); }); })
       .def("field_changed", [](SolverHandle& h) { h.visit([](auto& s) { s.field_changed(); }); },
            "the caller wrote the field: re-exchange the ghost ring and re-check the sum form's range next run")
       .def(

@@ -55,19 +55,23 @@ StencilSolver<T>::StencilSolver(const CartTopology& topo, int rank, const TileGe
   block_ = cfg_.kind == StencilKind::Jacobi5 ? std::max(1, cfg_.time_block) : 1;
   // Chebyshev relaxation: its preconditions are configuration and topology,
   // the same on every rank, so every rank throws or none does.
-  relax_ = cfg_.relaxation == Relaxation::Chebyshev;
+  // A source term runs the same cycles (a uniform table without Chebyshev) and
+  // has the same preconditions.
+  cheb_ = cfg_.relaxation == Relaxation::Chebyshev;
+  relax_ = cheb_ || cfg_.source;
+  const char* const mode_name = cheb_ ? "relaxation = chebyshev" : "source = true";
   if (relax_) {
     MXS_CHECK(cfg_.kind == StencilKind::Jacobi5,
-              "relaxation = chebyshev needs the 5-point Jacobi stencil (this solver runs the box stencil)");
+              mode_name << " needs the 5-point Jacobi stencil (this solver runs the box stencil)");
     MXS_CHECK(!topo.periodic_rows && !topo.periodic_cols,
-              "relaxation = chebyshev needs fixed edges on both axes: the topology is periodic in "
+              mode_name << " needs fixed edges on both axes: the topology is periodic in "
                   << (topo.periodic_rows && topo.periodic_cols ? "both axes" : topo.periodic_rows ? "the rows" : "the columns")
                   << " (the periodic operator is singular)");
     MXS_CHECK(cfg_.block_fixed_edges,
-              "relaxation = chebyshev needs block_fixed_edges: a cycle is one time-blocked pass beside the fixed edges");
+              mode_name << " needs block_fixed_edges: a cycle is one time-blocked pass beside the fixed edges");
     MXS_CHECK(cfg_.global_width > 0 && cfg_.global_height > 0,
-              "relaxation = chebyshev needs the global grid size (SolverConfig::global_width / global_height)");
-    kernels::chebyshev_check(cfg_.global_width, cfg_.global_height, cfg_.coeffs.center, cfg_.coeffs.neighbor);
+              mode_name << " needs the global grid size (SolverConfig::global_width / global_height)");
+    if (cheb_) kernels::chebyshev_check(cfg_.global_width, cfg_.global_height, cfg_.coeffs.center, cfg_.coeffs.neighbor);
     // Automatic time block: the deeper cycle unless it exceeds the tile.
     if (cfg_.time_block <= 0) block_ = kernels::relaxation_auto_depth(int(sizeof(T)), tile_.width, tile_.height);
     // One coefficient pair per level: the per-step form.
@@ -102,7 +106,7 @@ StencilSolver<T>::StencilSolver(const CartTopology& topo, int rank, const TileGe
   }
   MXS_CHECK(block_ <= kernels::kMaxTimeBlockDeep, "time_block must be <= " << kernels::kMaxTimeBlockDeep);
   MXS_CHECK(!relax_ || kernels::relaxation_depth_supported(int(sizeof(T)), block_),
-            "relaxation = chebyshev needs an agreed time block of "
+            mode_name << " needs an agreed time block of "
                 << (sizeof(T) == 4 ? "20 or 24 (fp32)" : "12 or 16 (fp64)") << ", got " << block_
                 << " (requested " << cfg_.time_block << "; blocks past 16 need fp32 and a tile width of whole 4-cell vectors)");
   MXS_CHECK(block_ <= tile_.width && block_ <= tile_.height,
@@ -234,8 +238,24 @@ StencilSolver<T>::StencilSolver(const CartTopology& topo, int rank, const TileGe
     sum_note_ = fast_form_note(v);
   }
   cfg_.coeffs.sum_form = user_sum_ && sum_coeffs_ok_;
-  if (relax_) {
-    sum_note_ = "fast form off: relaxation = chebyshev runs the per-step form (one coefficient pair per level)";
+  if (relax_ && !cheb_) {
+    // The source's uniform table: every level the base pair, weight 1 (plain
+    // Jacobi, bitwise the per-step pass). Configuration only: nothing to agree.
+    sum_note_ = "fast form off: source = true runs the per-step form (the level-table passes carry the source)";
+    levels_.n = block_;
+    for (int l = 0; l < block_; ++l) {
+      levels_.center[l] = cfg_.coeffs.center;
+      levels_.neighbor[l] = cfg_.coeffs.neighbor;
+      omega_[l] = 1.0;
+    }
+    levels_.growth = 1.0;
+    omega_min_ = omega_max_ = 1.0;
+    relax_on_ = true;
+  }
+  if (cheb_) {
+    sum_note_ = cfg_.source ? "fast form off: source = true and relaxation = chebyshev run the per-step form (one "
+                              "coefficient pair per level)"
+                            : "fast form off: relaxation = chebyshev runs the per-step form (one coefficient pair per level)";
     // The table is computed once, on rank 0, and every rank adopts its bits
     // (the other ranks contribute zeros to an exact sum), so all tiles run the
     // same coefficients whatever each host's libm returns.
@@ -255,6 +275,7 @@ StencilSolver<T>::StencilSolver(const CartTopology& topo, int rank, const TileGe
       levels_.center[l] = v[size_t(l)];
       levels_.neighbor[l] = v[size_t(block_ + l)];
       const double w = kernels::relaxation_omega(levels_, cfg_.coeffs.neighbor, l);
+      omega_[l] = w;
       omega_min_ = l == 0 ? w : std::min(omega_min_, w);
       omega_max_ = l == 0 ? w : std::max(omega_max_, w);
     }
@@ -306,17 +327,19 @@ void StencilSolver<T>::core_pass(const T* cur, T* nxt, int S, hipStream_t s) {
   // A relaxation cycle: the same split, the level-table kernels. (A pass of
   // another depth is a warm-up of prepare() / warm() into scratch: plain.)
   const bool levels = relax_on_ && S == levels_.n;
+  // With a source the cycle's correction rides in every launch of the pass.
+  const T* const corr = levels && src_set_ ? src_G_.get() : nullptr;
   if (hold_ == 0 || S <= 1) {
-    if (levels) return kernels::stencil5_tb_levels<T>(cur, nxt, tile_, 0, w, 0, h, levels_, s);
+    if (levels) return kernels::stencil5_tb_levels<T>(cur, nxt, tile_, 0, w, 0, h, levels_, corr, s);
     return update(cur, nxt, S, 0, w, 0, h, s);
   }
   const kernels::FixedEdgeSplit sp = kernels::fixed_edge_split(w, h, S, kFixedEdgeVec, hold_);
   const kernels::Rect& in = sp.interior;
-  if (levels) kernels::stencil5_tb_levels<T>(cur, nxt, tile_, in.x0, in.x1, in.y0, in.y1, levels_, s);
+  if (levels) kernels::stencil5_tb_levels<T>(cur, nxt, tile_, in.x0, in.x1, in.y0, in.y1, levels_, corr, s);
   else update(cur, nxt, S, in.x0, in.x1, in.y0, in.y1, s);
   for (int i = 0; i < sp.n_frame; ++i) {
     const kernels::Rect& f = sp.frame[i];
-    if (levels) kernels::stencil5_tb_held_levels<T>(cur, nxt, tile_, f.x0, f.x1, f.y0, f.y1, levels_, hold_, s);
+    if (levels) kernels::stencil5_tb_held_levels<T>(cur, nxt, tile_, f.x0, f.x1, f.y0, f.y1, levels_, hold_, corr, s);
     else kernels::stencil5_tb_held<T>(cur, nxt, tile_, S, f.x0, f.x1, f.y0, f.y1, cfg_.coeffs, hold_, s);
   }
 }
@@ -325,8 +348,12 @@ template <typename T>
 std::string StencilSolver<T>::relaxation_note() const {
   if (!relax_) return "";
   char buf[256];
-  std::snprintf(buf, sizeof(buf), "chebyshev: M = %d, omega in [%.4g, %.4g], growth %.4g; ", levels_.n, omega_min_,
-                omega_max_, levels_.growth);
+  if (cheb_)
+    std::snprintf(buf, sizeof(buf), "chebyshev: M = %d, omega in [%.4g, %.4g], growth %.4g; ", levels_.n, omega_min_,
+                  omega_max_, levels_.growth);
+  else std::snprintf(buf, sizeof(buf), "uniform level table (source = true): M = %d; ", levels_.n);
+  if (relax_on_ && src_set_)
+    return std::string(buf) + "level passes with the source's correction (the field is the iterate at cycle ends only)";
   if (relax_on_) return std::string(buf) + "level passes (the field is meaningful at cycle ends only)";
   return std::string(buf) + "plain per-step passes: " + relax_guard_;
 }
@@ -575,6 +602,12 @@ void StencilSolver<T>::ensure_range(bool collective) {
   // measurement may only switch the cycle off.
   if (relax_) {
     const bool fits = kernels::relaxation_range_ok<T>(levels_, md) && (agreed || relax_on_);
+    // The correction belongs to the table: no falling back to the plain pass.
+    MXS_CHECK(fits || !src_set_,
+              "the relaxation range guard failed while a source is set: growth "
+                  << levels_.growth << " x max|u| " << md
+                  << " is not below max(T) / 4, and the source's correction belongs to the level table (no fallback "
+                     "to the plain pass)");
     if (fits != relax_on_) {
       relax_on_ = fits;
       char buf[160];
@@ -623,7 +656,8 @@ void StencilSolver<T>::run(int iters) {
   last_forks_ = 0;
   if (iters <= 0) return;
   MXS_CHECK(!relax_ || iters % block_ == 0,
-            "run(" << iters << "): with relaxation = chebyshev the cycle is the unit of progress, so the iteration "
+            "run(" << iters << "): with " << (cheb_ ? "relaxation = chebyshev" : "source = true")
+                   << " the cycle is the unit of progress, so the iteration "
                    << "count must be a multiple of the cycle length " << block_);
   maybe_stall("run");
   begin_run(false);
@@ -969,7 +1003,7 @@ Residual StencilSolver<T>::residual() {
   if (!residual_counter_.get()) residual_counter_.reset(1);
   auto* norms = reinterpret_cast<kernels::ResidualNorms*>(residual_buf_.get());
   kernels::stencil5_residual<T>(cur_, tile_, cfg_.coeffs, norms, residual_buf_.get() + 2, residual_counter_.get(),
-                                main_.get());
+                                main_.get(), src_set_ ? src_g_.get() : nullptr);
   kernels::ResidualNorms h{0.0, 0.0};
   MXS_HIP_CHECK(hipMemcpyAsync(&h, norms, sizeof(h), hipMemcpyDeviceToHost, main_.get()));
   wait_idle("residual");
@@ -990,6 +1024,55 @@ Residual StencilSolver<T>::residual() {
   }
   r.l2 = std::sqrt(sumsq);
   return r;
+}
+
+template <typename T>
+void StencilSolver<T>::set_source(const T* g_tile) {
+  MXS_TRACE_RANGE("stencil.set_source");
+  MXS_CHECK(cfg_.source, "set_source: this solver was built without a source term (SolverConfig::source)");
+  maybe_stall("set_source");
+  join_side();
+  wait_idle("set_source");
+  // Captured launches hold the correction pointer (or its absence).
+  graphs_.clear();
+  warmed_.clear();
+  src_set_ = false;
+  if (g_tile == nullptr) return field_changed();
+  hipStream_t m = main_.get();
+  const index_t elems = tile_.alloc_elems();
+  const size_t bytes = size_t(elems) * sizeof(T);
+  if (src_g_.size() < elems) src_g_.reset(elems);
+  if (src_G_.size() < elems) src_G_.reset(elems);
+  T* const tmp = scratch_tiles(1);
+  MXS_CHECK(tmp != nullptr, "set_source: no room for the build's temporary tile");
+  MXS_HIP_CHECK(hipMemcpyAsync(src_g_.get(), g_tile, bytes, hipMemcpyDeviceToDevice, m));
+  // G_0 = 0 on a tile whose ring is 0: physical sides stay 0 (no step or
+  // exchange writes them), the others carry the neighbours' G_l.
+  MXS_HIP_CHECK(hipMemsetAsync(src_G_.get(), 0, bytes, m));
+  MXS_HIP_CHECK(hipMemsetAsync(tmp, 0, bytes, m));
+  T* a = src_G_.get();
+  T* b = tmp;
+  ex_->set_copy_block(0);
+  for (int l = 0; l < levels_.n; ++l) {
+    ex_->exchange(a, m);
+    const kernels::Stencil5Coeffs c{levels_.center[l], levels_.neighbor[l], false, -1.0};
+    kernels::stencil5_rows<T>(a, b, tile_, 0, tile_.height, c, m, cfg_.variant);
+    kernels::source_axpy<T>(b, src_g_.get(), tile_, omega_[l], m);
+    std::swap(a, b);
+  }
+  if (a != src_G_.get()) MXS_HIP_CHECK(hipMemcpyAsync(src_G_.get(), a, bytes, hipMemcpyDeviceToDevice, m));
+  if (!absmax_.get()) absmax_.reset(1);
+  kernels::absmax<T>(src_G_.get(), elems, absmax_.get(), m);
+  T top = T(0);
+  MXS_HIP_CHECK(hipMemcpyAsync(&top, absmax_.get(), sizeof(T), hipMemcpyDeviceToHost, m));
+  wait_idle("set_source");
+  // Every rank must take the same branch: agree before throwing.
+  std::vector<double> bad{std::isfinite(double(top)) ? 0.0 : 1.0};
+  agree_max(bad, "set_source: correction agreement");
+  MXS_CHECK(bad[0] == 0.0, "set_source: the cycle's correction G is not finite (the source or the level table overflows "
+                           "the element type)");
+  src_set_ = true;
+  field_changed();
 }
 
 template <typename T>

@@ -85,6 +85,17 @@ class StencilConfig:
     # fp32 stalls at a rounding floor (docs/ARCHITECTURE.md); use f64 for tight
     # tolerances. "none": plain Jacobi.
     relaxation: str = "none"
+    # This solver takes a source term, u' = A u + g (Stencil2D.set_source): the
+    # Poisson problem. One cycle with a source is the homogeneous level-table
+    # pass plus a correction G, built once per set_source, added where the pass
+    # stores (docs/ARCHITECTURE.md "Source term"). Needs, on every backend,
+    # jacobi5, periodic=False, block_fixed_edges and a time block with level
+    # kernels (fp32 20 / 24, fp64 12 / 16; time_block=0 picks 24 / 16). With
+    # relaxation="none" the passes run a uniform level table of time_block
+    # levels (plain Jacobi). Either way the per-step form runs, the cycle is the
+    # unit of progress (run(K) needs K % M == 0) and the field is the iterate at
+    # cycle ends only.
+    source: bool = False
     seed: int = 1234
     init: str = "random"             # random | rank
     graph_supersteps: int = 0        # super-steps per hipGraph launch (0 = auto, ~1 ms of work)
@@ -156,6 +167,21 @@ class StencilConfig:
                                  "sides: the periodic operator is singular)")
             if self.init == "rank":
                 raise ValueError("StencilConfig: relaxation='chebyshev' does not run the reference's exchange-only init")
+        if self.source:
+            if self.kind != "jacobi5":
+                raise ValueError("StencilConfig: source=True needs kind='jacobi5' (the 5-point Jacobi stencil)")
+            if self.periodic:
+                raise ValueError("StencilConfig: source=True needs periodic=False (fixed edges on all four sides: the "
+                                 "periodic operator is singular)")
+            if not self.block_fixed_edges:
+                raise ValueError("StencilConfig: source=True needs block_fixed_edges=True (a cycle is one time-blocked "
+                                 "pass beside the fixed edges)")
+            if self.init == "rank":
+                raise ValueError("StencilConfig: source=True does not run the reference's exchange-only init")
+            depths = (20, 24) if self.dtype == "f32" else (12, 16)
+            if self.time_block > 0 and self.time_block not in depths:
+                raise ValueError(f"StencilConfig: source=True needs a time block with level kernels ({self.dtype}: "
+                                 f"{depths[0]} or {depths[1]}; 0 picks {depths[1]}), got time_block={self.time_block}")
         if not 0.0 <= self.min_gain < 1.0 or self.wire_delay_us < 0 or self.halo_max_ctas < 0:
             raise ValueError("StencilConfig: min_gain in [0, 1), wire_delay_us >= 0, halo_max_ctas >= 0")
 
@@ -186,7 +212,10 @@ class Stencil2D:
         # A relaxation cycle is one time block: the deeper level kernels' depth
         # unless it exceeds the tile (the native solver's rule).
         self.relaxation = cfg.relaxation == "chebyshev"
-        if self.relaxation and tb <= 0 and dev.type == "cuda":
+        self.source = bool(cfg.source)  # a source's cycles are level-table cycles too (a uniform table)
+        self._g_core = None  # torch backend: this rank's slice of g and the cycle's correction G
+        self._G = None
+        if (self.relaxation or self.source) and tb <= 0 and dev.type == "cuda":
             big, small = (24, 20) if cfg.dtype == "f32" else (16, 12)
             tb = int(self.ctx.allreduce_min(big if big <= min(d.width, d.height) else small))
         # A fast form may run: the sum form (equal coefficients) or the scaled
@@ -273,7 +302,7 @@ class Stencil2D:
                                           cfg.wire_delay_us, cfg.direct_engine, cfg.steady,
                                           block_fixed_edges=bool(cfg.block_fixed_edges and not cfg.periodic),
                                           relaxation=cfg.relaxation, global_width=cfg.global_width,
-                                          global_height=cfg.global_height)
+                                          global_height=cfg.global_height, source=self.source)
             # The solver may cap the request (blocks > 16 need the fp32 pipeline's
             # preconditions); the ghost ring was sized for the request.
             self.time_block = self.solver.time_block()
@@ -282,13 +311,16 @@ class Stencil2D:
             self.plan = make_plan(d, self.geom, corners=True)
             self.halo = TorchHalo(self.plan, self.ctx)
             self.cycle = 0
+            if self.relaxation or self.source:
+                self.cycle = cfg.time_block if cfg.time_block > 1 else (24 if cfg.dtype == "f32" else 16)
+                # A source without Chebyshev: the uniform table, every level the base pair.
+                self._levels = ([cfg.c_center] * self.cycle, [cfg.c_neighbor] * self.cycle, 1.0)
             if self.relaxation:
                 # The same schedule one iteration at a time: iteration t runs
                 # level t mod M through ops.stencil5. The table is the native
                 # function's, rank 0's bits on every rank.
                 import struct
 
-                self.cycle = cfg.time_block if cfg.time_block > 1 else (24 if cfg.dtype == "f32" else 16)
                 t = C.chebyshev_cycle(cfg.global_width, cfg.global_height, cfg.c_center, cfg.c_neighbor, self.cycle)
                 blob = struct.pack(f"<{2 * self.cycle + 1}d", *t["center"], *t["neighbor"], t["growth"])
                 v = struct.unpack(f"<{2 * self.cycle + 1}d", self.ctx.allgather_bytes(blob)[0])
@@ -380,7 +412,8 @@ class Stencil2D:
         if iters <= 0:
             return
         if self.cycle and iters % self.cycle:
-            raise ValueError(f"run({iters}): with relaxation='chebyshev' the cycle is the unit of progress, so the "
+            mode = "relaxation='chebyshev'" if self.relaxation else "source=True"
+            raise ValueError(f"run({iters}): with {mode} the cycle is the unit of progress, so the "
                              f"iteration count must be a multiple of the cycle length {self.cycle}")
         if self.solver is not None:
             self.solver.run(iters)
@@ -427,9 +460,83 @@ class Stencil2D:
         elif self.cycle:  # level t mod M of the cycle
             lvl = self.iteration % self.cycle
             ops.stencil5(self._cur, self._nxt, g, 0, g.height, self._levels[0][lvl], self._levels[1][lvl])
+            if self._G is not None and lvl == self.cycle - 1:  # the cycle's correction, one rounded add per cell
+                out = self._core_of(self._nxt)
+                out.copy_(out + self._G)
         else:
             ops.stencil5(self._cur, self._nxt, g, 0, g.height, cfg.c_center, cfg.c_neighbor)
         self._cur, self._nxt = self._nxt, self._cur
+
+    def _core_of(self, tile: torch.Tensor) -> torch.Tensor:
+        g = self.geom
+        x0 = g.x_origin + g.halo_x
+        return tile.view(g.total_height(), g.pitch)[g.halo_y:g.halo_y + g.height, x0:x0 + g.width]
+
+    def set_source(self, g):
+        """Collective: the source term ``g`` of ``u' = A u + g`` (``StencilConfig.source``):
+        a scalar, a 2-D tensor over the GLOBAL grid (``global_height x global_width``,
+        any device; each rank takes its core's slice) or ``None``, which clears the
+        source. ``g`` is the additive term of one base Jacobi step; for
+        ``-laplace(u) = f`` with the 5-point average it is ``c_neighbor h^2 f``.
+
+        Builds the cycle's correction ``G`` (``G_0 = 0``, ``G_{l+1} = C_l G_l + w_l g``:
+        one single step and one halo exchange per level, on a tile whose ring is 0
+        on physical sides), which every later cycle adds where it stores;
+        ``residual()`` becomes ``A u + g - u``. Drops captured graphs and ends like
+        ``field_changed()``. Until it is called the solver runs the homogeneous
+        level passes. The source is not part of a checkpoint: call it again
+        after ``load_checkpoint``."""
+        if not self.source:
+            raise ValueError("set_source: this solver was built without a source term (StencilConfig.source=True)")
+        d, geom = self.decomp, self.geom
+        tile = None
+        if g is not None:
+            tile = torch.zeros(geom.alloc_elems(), dtype=self.dtype, device=self.device)
+            if isinstance(g, torch.Tensor):
+                if g.dim() != 2 or tuple(g.shape) != (d.global_height, d.global_width):
+                    raise ValueError(f"set_source: g must be a scalar or a 2-D tensor of shape (global_height, "
+                                     f"global_width) = ({d.global_height}, {d.global_width}); got {tuple(g.shape)}")
+                mine = g[d.y0:d.y0 + d.height, d.x0:d.x0 + d.width].to(device=self.device, dtype=self.dtype)
+            else:
+                mine = torch.full((d.height, d.width), float(g), dtype=self.dtype, device=self.device)
+            self._core_of(tile).copy_(mine)
+        self.synchronize()
+        if self.solver is not None:
+            if self.device.type == "cuda":
+                torch.cuda.synchronize()
+            self.solver.set_source(tile.data_ptr() if tile is not None else 0)  # the solver keeps its own copies
+            return
+        self._g_core, self._G = None, None
+        if tile is not None:
+            from ..ops.source import level_omega
+
+            g_core = self._core_of(tile).clone()
+            a, b = torch.zeros_like(tile), torch.zeros_like(tile)
+            for c0, c1 in zip(self._levels[0], self._levels[1]):
+                self.halo.exchange(a)
+                ops.stencil5(a, b, geom, 0, geom.height, c0, c1)
+                p = torch.tensor(level_omega(c1, self.cfg.c_neighbor), dtype=self.dtype, device=self.device) * g_core
+                out = self._core_of(b)
+                out.copy_(out + p)
+                a, b = b, a
+            G = self._core_of(a).clone()
+            finite = bool(torch.isfinite(G).all())
+            if self.ctx.allreduce_max(0.0 if finite else 1.0) != 0.0:
+                raise RuntimeError("set_source: the cycle's correction G is not finite (the source or the level table "
+                                   "overflows the element type)")
+            self._g_core, self._G = g_core, G
+        self.field_changed()
+
+    def source_correction(self) -> torch.Tensor | None:
+        """This rank's core of the cycle's correction ``G`` (a copy; ``None`` while
+        no source is set)."""
+        if self.solver is None:
+            return None if self._G is None else self._G.clone()
+        flat = torch.empty(self.geom.alloc_elems(), dtype=self.dtype, device=self.device)
+        torch.cuda.synchronize()
+        if not self.solver.copy_source_correction(flat.data_ptr()):
+            return None
+        return self._core_of(flat).clone()
 
     def relaxation_note(self) -> str:
         """The relaxation cycle: which passes run and why (the level passes, or the
@@ -441,6 +548,9 @@ class Stencil2D:
         if not self.cycle:
             return ""
         info = self.relaxation_info()
+        if not self.relaxation:
+            return (f"uniform level table (source=True): M = {self.cycle}; one level per iteration through "
+                    "ops.stencil5 (the field is the iterate at cycle ends only)")
         return (f"chebyshev: M = {self.cycle}, omega in [{info['omega_min']:.4g}, {info['omega_max']:.4g}], "
                 f"growth {info['growth']:.4g}; one level per iteration through ops.stencil5 (the field is meaningful "
                 "at cycle ends only)")
@@ -453,7 +563,7 @@ class Stencil2D:
             return {k: i[k] for k in ("cycle", "omega_min", "omega_max", "growth")}
         if not self.cycle:
             return {"cycle": 0, "omega_min": 0.0, "omega_max": 0.0, "growth": 0.0}
-        omega = [n / self.cfg.c_neighbor for n in self._levels[1]]
+        omega = [1.0 if n == self.cfg.c_neighbor else n / self.cfg.c_neighbor for n in self._levels[1]]
         return {"cycle": self.cycle, "omega_min": min(omega), "omega_max": max(omega), "growth": self._levels[2]}
 
     # ---------------------------------------------------------- convergence
@@ -463,6 +573,7 @@ class Stencil2D:
 
     def residual(self) -> dict:
         """Collective (jacobi5): the norms of the Jacobi residual ``r = A u - u``
+        (``A u + g - u`` once ``set_source`` set a source)
         over the global core — exactly the change the next single step would
         make — agreed over ranks: ``{"linf": max |r|, "l2": sqrt(sum r^2),
         "cells": global cells}``. It needs the current field and a fresh 1-deep
@@ -480,7 +591,8 @@ class Stencil2D:
         if self.device.type == "cuda":
             torch.cuda.synchronize()
         v = self._cur.view(g.total_height(), g.pitch)[:, g.x_origin:g.x_origin + g.total_width()]
-        linf, l2 = ops.residual5_reference(v, (g.halo_y, g.halo_x), self.cfg.c_center, self.cfg.c_neighbor)
+        linf, l2 = ops.residual5_reference(v, (g.halo_y, g.halo_x), self.cfg.c_center, self.cfg.c_neighbor,
+                                           source=self._g_core)
         # A NaN travels as +inf (a max of NaNs depends on the order); the squares
         # are summed in rank order, so every rank gets the same bits.
         linf = self.ctx.allreduce_max(linf if math.isfinite(linf) else math.inf)
@@ -778,6 +890,10 @@ def main(argv=None) -> int:
     p.add_argument("--relaxation", default="none", choices=["none", "chebyshev"],
                    help="chebyshev: each time block is one Chebyshev cycle (needs --non-periodic --block-fixed-edges; "
                         "--iters, --warmup and --check-every in whole cycles; the field is meaningful at cycle ends)")
+    p.add_argument("--source", type=float, default=None, metavar="Q",
+                   help="a constant source term g = Q everywhere (u' = A u + g); implies --non-periodic and "
+                        "--block-fixed-edges and needs a time block with level kernels (fp32 20 / 24, fp64 12 / 16; "
+                        "the default picks one); --iters, --warmup and --check-every in whole cycles")
     p.add_argument("--tol", type=float, default=None,
                    help="iterate until the residual norm is <= TOL (run_until) instead of --iters iterations; "
                         "the timed region is the run_until")
@@ -797,13 +913,18 @@ def main(argv=None) -> int:
         gw, gh = lw * cols, lh * rows
     else:
         gw, gh = _parse_wh(args.global_ or "8192x8192")
+    if args.source is not None:  # the source's preconditions come with it
+        args.non_periodic = args.block_fixed_edges = True
     cfg = StencilConfig(global_width=gw, global_height=gh, dims=f"{rows}x{cols}", dtype=args.dtype,
                         backend=args.backend, overlap=False if args.no_overlap else None, graph=not args.no_graph,
                         loopback=args.loopback, variant=args.variant, time_block=args.time_block,
                         seed=args.seed, opening=args.opening, steady=args.steady, c_center=args.c_center,
                         c_neighbor=args.c_neighbor, sum_form=not args.no_sum_form, periodic=not args.non_periodic,
-                        block_fixed_edges=args.block_fixed_edges, relaxation=args.relaxation)
+                        block_fixed_edges=args.block_fixed_edges, relaxation=args.relaxation,
+                        source=args.source is not None)
     st = Stencil2D(cfg, ctx)
+    if args.source is not None:
+        st.set_source(args.source)
     if args.resume:
         hdr = st.load_checkpoint(args.resume)
         if ctx.is_root:
@@ -840,7 +961,7 @@ def main(argv=None) -> int:
                           else "per step")}
     info = st.relaxation_info()
     rec.update(relaxation=cfg.relaxation, cycle=info["cycle"], omega_min=info["omega_min"], omega_max=info["omega_max"],
-               cycle_growth=info["growth"], relaxation_note=st.relaxation_note())
+               cycle_growth=info["growth"], relaxation_note=st.relaxation_note(), source=args.source)
     if until is not None:
         rec.update(converged=until["converged"], iterations=until["iterations"], residual=until["residual"],
                    checks=until["checks"], norm=until["norm"], reason=until["reason"], tol=args.tol,

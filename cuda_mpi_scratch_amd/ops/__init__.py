@@ -4,6 +4,7 @@ from .dot import DotWorkspace, dot  # noqa: F401
 from .fill import fill, fill_random, fill_region, random_values  # noqa: F401
 from .relaxation import (chebyshev_cycle, jacobi_held_levels_reference, relaxation_spectrum,  # noqa: F401
                          stencil5_tb_held_levels, stencil5_tb_levels)
+from .source import jacobi_source_per_step_reference, source_correction_reference  # noqa: F401
 from .stencil import (HOLD_BOTTOM, HOLD_LEFT, HOLD_RIGHT, HOLD_TOP, box_reference,  # noqa: F401
                       jacobi_held_reference, jacobi_reference_global, jacobi_sum_reference_global,
                       residual5_reference, stencil5, stencil5_rect, stencil5_reference, stencil5_residual,

@@ -84,30 +84,41 @@ def _levels(center, neighbor):
     return center, neighbor
 
 
-def stencil5_tb_levels(src, dst, geom, x0, x1, y0, y1, center, neighbor, stream=None) -> None:
+def _corr_ptr(corr, src, geom, who) -> int:
+    if corr is None:
+        return 0
+    if corr.dtype != src.dtype or corr.device != src.device or corr.numel() < geom.alloc_elems():
+        raise ValueError(f"{who}: corr must be a tile of the pass's geometry, dtype and device")
+    return corr.data_ptr()
+
+
+def stencil5_tb_levels(src, dst, geom, x0, x1, y0, y1, center, neighbor, stream=None, corr=None) -> None:
     """One pass of ``len(center)`` levels over core rectangle [x0, x1) x [y0, y1)
     of a ghost-ring tile at least that deep (GPU tensors only): level ``l`` is
     one Jacobi step with ``(center[l], neighbor[l])``. The contract of the
     per-step ``stencil5_tb`` without wrap, plus the table; bitwise equal to the
-    single steps. Depths: fp32 20 / 24, fp64 12 / 16."""
+    single steps. Depths: fp32 20 / 24, fp64 12 / 16. ``corr``: a tile of the same
+    geometry (a source term's correction); the pass then ends with
+    ``dst += corr`` on the rectangle, one rounded add per cell, in the same
+    launch, and reads only the rectangle's cells of ``corr``."""
     if not src.is_cuda:
         raise TypeError("stencil5_tb_levels runs the HIP kernels: GPU tensors only (CPU: jacobi_held_levels_reference)")
     center, neighbor = _levels(center, neighbor)
     hip().stencil5_tb_levels(src.data_ptr(), dst.data_ptr(), geom, x0, x1, y0, y1, center, neighbor, dtype_name(src),
-                             _stream(stream))
+                             _stream(stream), _corr_ptr(corr, src, geom, "stencil5_tb_levels"))
 
 
-def stencil5_tb_held_levels(src, dst, geom, x0, x1, y0, y1, center, neighbor, hold=15, stream=None) -> None:
+def stencil5_tb_held_levels(src, dst, geom, x0, x1, y0, y1, center, neighbor, hold=15, stream=None, corr=None) -> None:
     """``stencil5_tb_held`` with a level table: cells outside the core on a held
     side (``hold``: HOLD_* bits) keep their input value at every level; level
-    ``l`` runs ``(center[l], neighbor[l])``. GPU tensors only; depths as for
-    ``stencil5_tb_levels``."""
+    ``l`` runs ``(center[l], neighbor[l])``. GPU tensors only; depths and ``corr``
+    as for ``stencil5_tb_levels``."""
     if not src.is_cuda:
         raise TypeError("stencil5_tb_held_levels runs the HIP kernel: GPU tensors only "
                         "(CPU: jacobi_held_levels_reference)")
     center, neighbor = _levels(center, neighbor)
     hip().stencil5_tb_held_levels(src.data_ptr(), dst.data_ptr(), geom, x0, x1, y0, y1, center, neighbor, int(hold),
-                                  dtype_name(src), _stream(stream))
+                                  dtype_name(src), _stream(stream), _corr_ptr(corr, src, geom, "stencil5_tb_held_levels"))
 
 
 def _round_to_odd_sum(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:

@@ -193,29 +193,42 @@ def jacobi_sum_reference_global(u: torch.Tensor, steps: int, c: float = 0.2) -> 
     return v * torch.tensor(c_t ** steps, dtype=torch.float64).to(u.dtype)
 
 
-def stencil5_residual(src: torch.Tensor, geom, c_center: float = 0.2, c_neighbor: float = 0.2, stream=None):
+def stencil5_residual(src: torch.Tensor, geom, c_center: float = 0.2, c_neighbor: float = 0.2, stream=None,
+                      source: torch.Tensor | None = None):
     """``(linf, sumsq)`` of the Jacobi residual ``r = A u - u`` over the core of a
     ghost-ring tile: ``r = fma(c_neighbor, (n + s) + (w + e), c_center * v) - v``
     per cell in the element type, ``linf = max |r|`` (NaN if any is),
     ``sumsq = sum r^2`` in float64. GPU tensors run the HIP kernel
     (``csrc/kernels/residual.hip``: one streaming read of the core and the ring
-    cells beside it, deterministic); CPU tensors the reference expression."""
+    cells beside it, deterministic); CPU tensors the reference expression.
+    ``source``: a tile of the same geometry whose core holds ``g`` of
+    ``u' = A u + g``; then ``r = (fma(...) + g) - v``, each one rounded
+    operation, and only core cells of ``source`` are read."""
     if geom.halo_x < 1 or geom.halo_y < 1:
         raise ValueError("stencil5_residual: the tile has no ghost ring (it needs one at least 1 deep)")
+    if source is not None and (source.dtype != src.dtype or source.device != src.device
+                               or source.numel() < geom.alloc_elems()):
+        raise ValueError("stencil5_residual: source must be a tile of the field's geometry, dtype and device")
     if src.is_cuda:
         linf, sumsq = hip().stencil5_residual(src.data_ptr(), geom, c_center, c_neighbor, dtype_name(src),
-                                              _stream(stream))
+                                              _stream(stream), source.data_ptr() if source is not None else 0)
         return float(linf), float(sumsq)
-    v = src.view(geom.total_height(), geom.pitch)[:, geom.x_origin:geom.x_origin + geom.total_width()]
-    r = _residual_field(v, (geom.halo_y, geom.halo_x), c_center, c_neighbor)
+    cols = slice(geom.x_origin, geom.x_origin + geom.total_width())
+    v = src.view(geom.total_height(), geom.pitch)[:, cols]
+    g = None
+    if source is not None:
+        g = source.view(geom.total_height(), geom.pitch)[:, cols][geom.halo_y:geom.halo_y + geom.height,
+                                                                  geom.halo_x:geom.halo_x + geom.width]
+    r = _residual_field(v, (geom.halo_y, geom.halo_x), c_center, c_neighbor, g)
     return float(r.abs().max()) if r.numel() else 0.0, float((r * r).sum())
 
 
-def _residual_field(full: torch.Tensor, ring, c_center, c_neighbor) -> torch.Tensor:
+def _residual_field(full: torch.Tensor, ring, c_center, c_neighbor, source=None) -> torch.Tensor:
     """float64 residual of every core cell of a (total_height, total_width) view
     whose ring is ``ring`` = (rows, columns) deep: the stencil value rounded to
-    the element type (jacobi_reference_global's arithmetic), minus the cell,
-    rounded to the element type again."""
+    the element type (jacobi_reference_global's arithmetic), plus the core-sized
+    ``source`` if there is one (rounded), minus the cell, rounded to the element
+    type again."""
     ry, rx = (ring, ring) if isinstance(ring, int) else ring
     if ry < 1 or rx < 1:
         raise ValueError("residual5_reference: the view has no ghost ring (it needs one at least 1 deep)")
@@ -230,15 +243,19 @@ def _residual_field(full: torch.Tensor, ring, c_center, c_neighbor) -> torch.Ten
         new = (c1 * sums.double() + prod).float()
     else:
         new = c_neighbor * sums + c_center * c
+    if source is not None:
+        new = new + source.to(dtype=full.dtype, device=full.device)
     return (new - c).double()
 
 
-def residual5_reference(full: torch.Tensor, ring, c_center: float = 0.2, c_neighbor: float = 0.2):
+def residual5_reference(full: torch.Tensor, ring, c_center: float = 0.2, c_neighbor: float = 0.2, source=None):
     """CPU reference of the residual norms on a ``(total_height, total_width)``
     view (core + a ghost ring ``ring`` cells deep, an int or (rows, columns)):
     ``(linf, l2)`` of ``A u - u`` over the core, reduced in float64. Only the
-    ring cells beside the core enter."""
-    r = _residual_field(full.detach().cpu(), ring, c_center, c_neighbor)
+    ring cells beside the core enter. ``source``: a core-sized 2-D tensor ``g``;
+    then the norms are those of ``A u + g - u``."""
+    r = _residual_field(full.detach().cpu(), ring, c_center, c_neighbor,
+                        None if source is None else source.detach().cpu())
     if r.numel() == 0:
         return 0.0, 0.0
     return float(r.abs().max()), float(torch.sqrt((r * r).sum()))
