@@ -12,6 +12,8 @@
 //          stencil5_residual (norms of A u - u)  kernels/residual.hip
 //   K13    level passes with a correction tile, source_axpy (the source term)
 //                                                kernels/stencil_pipe_levels_src_f32/_f64.hip, stencil_levels_src.hip
+//          mg_smooth, mg_residual_restrict, mg_prolong_add, mg_coarse_solve (the multigrid V-cycle)
+//                                                kernels/multigrid.hip
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -23,6 +25,7 @@
 #include "mxs/grid/layout.hpp"
 #include "mxs/kernels/chunk_schedule.hpp"
 #include "mxs/kernels/fixed_edge_split.hpp"
+#include "mxs/kernels/multigrid.hpp"
 #include "mxs/kernels/pipe_form.hpp"
 #include "mxs/kernels/relaxation.hpp"
 
@@ -329,6 +332,39 @@ void stencil5_residual(const T* u, const TileGeom& g, Stencil5Coeffs c, Residual
 // src: a tile of geometry g whose core holds the additive term g of
 // u' = A u + g; the residual is then r = (fma(...) + g) - v, each one rounded
 // operation. Only core cells of src are read. Same grid, determinism and finish.
+
+// ------------------------------------------------- multigrid (kernels/multigrid.hip)
+// The four kernels of the geometric multigrid V-cycle for u = A u + g on a
+// core with a depth-1 Dirichlet ring (multigrid.hpp; docs/ARCHITECTURE.md
+// "Multigrid"). Every tile has a ghost ring at least 1 deep; only the cells
+// named are read or written, so rings and padding of the other tiles may hold
+// anything. Each is bitwise equal to its reference in ops/multigrid.py.
+//
+// mg_smooth: t.n (1..kMgMaxSmooth) sweeps in one launch ("mg_smooth"): reads
+// u_in (core and ring) and the core of src, writes the core of u_out; ring
+// cells are held. u_in != u_out. Any width, height >= 1.
+template <typename T>
+void mg_smooth(const T* u_in, T* u_out, const T* src, const TileGeom& g, const MgSweepTable& t, hipStream_t s);
+// mg_residual_restrict: the coarse right-hand side 4 R r of the fine residual
+// r = (A u + g) - u with full weighting R ("mg_residual_restrict"): reads u
+// (core and ring) and the core of src once, writes the core of coarse_src. The
+// coarse tile is ((width - 1) / 2) x ((height - 1) / 2), width and height odd.
+template <typename T>
+void mg_residual_restrict(const T* u, const T* src, const TileGeom& g, T* coarse_src, const TileGeom& gc,
+                          Stencil5Coeffs c, hipStream_t s);
+// mg_prolong_add: u core += P e, bilinear with e = 0 outside the coarse core
+// ("mg_prolong_add"): reads the core of e, reads and writes the core of u.
+template <typename T>
+void mg_prolong_add(const T* e, const TileGeom& gc, T* u, const TileGeom& g, hipStream_t s);
+// mg_coarse_solve: `repeats` x t.n sweeps from e = 0 on a grid of at most
+// kMgCoarsestMax x kMgCoarsestMax in one workgroup's LDS ("mg_coarse_solve"):
+// reads the core of src, writes the core of e.
+template <typename T>
+void mg_coarse_solve(const T* src, T* e, const TileGeom& g, const MgSweepTable& t, int repeats, hipStream_t s);
+// The kernel the most recent multigrid launcher of this host process ran (the
+// names above; "" before the first): a host-side record like
+// last_stencil_dispatch(), not updated by graph replays.
+const char* last_multigrid_dispatch();
 
 // Whether work on stream b runs while a kernel on stream a still runs (the two
 // sit on different hardware queues): one bounded ~0.8 ms sleeping wave on a, a

@@ -12,6 +12,7 @@
 #include "mxs/halo/plan.hpp"
 #include "mxs/kernels/chunk_schedule.hpp"
 #include "mxs/kernels/fixed_edge_split.hpp"
+#include "mxs/kernels/multigrid.hpp"
 #include "mxs/kernels/relaxation.hpp"
 #include "mxs/runtime/call_plan.hpp"
 #include "mxs/runtime/decision.hpp"
@@ -284,6 +285,50 @@ PYBIND11_MODULE(_mxs_core, m) {
       "per-level (center, neighbor) coefficients in Leja order and the prefix-polynomial growth; raises ValueError "
       "unless c_neighbor != 0 and the spectrum of I - A is positive");
   m.attr("MAX_LEVELS") = kernels::kMaxLevels;
+  // Multigrid: the level planner and the sweep tables (kernels/multigrid.hpp).
+  m.def(
+      "mg_plan_levels",
+      [](long long w, long long h) {
+        std::vector<std::pair<long long, long long>> out;
+        for (const kernels::MgLevel& l : kernels::mg_plan_levels(w, h)) out.emplace_back(l.width, l.height);
+        return out;
+      },
+      py::arg("width"), py::arg("height"),
+      "the multigrid levels of a width x height core, finest first, as (width, height) pairs: vertex-centred "
+      "coarsening (n - 1) / 2 of both axes together while both sides are odd, >= 3 and the larger is above 31; "
+      "raises ValueError when the coarsest level is above 63 on a side (the message names the nearest sizes that work)");
+  m.def("mg_check_operator", &kernels::mg_check_operator, py::arg("c_center"), py::arg("c_neighbor"),
+        "raises ValueError unless |c_center + 4 c_neighbor - 1| <= 1e-12 and c_neighbor > 0");
+  auto sweep_dict = [](const kernels::MgSweepTable& t) {
+    py::dict d;
+    d["n"] = t.n;
+    d["center"] = std::vector<double>(t.center, t.center + t.n);
+    d["neighbor"] = std::vector<double>(t.neighbor, t.neighbor + t.n);
+    d["weight"] = std::vector<double>(t.weight, t.weight + t.n);
+    return d;
+  };
+  m.def(
+      "mg_smoother_table",
+      [sweep_dict](double c0, double c1, double omega, int sweeps) {
+        return sweep_dict(kernels::mg_smoother_table(c0, c1, omega, sweeps));
+      },
+      py::arg("c_center"), py::arg("c_neighbor"), py::arg("omega"), py::arg("sweeps"),
+      "the damped-Jacobi smoother's per-sweep (center, neighbor, weight) table");
+  m.def(
+      "mg_coarse_plan",
+      [sweep_dict](long long w, long long h, double c0, double c1, double reduction) {
+        const kernels::MgCoarsePlan p = kernels::mg_coarse_plan(w, h, c0, c1, reduction);
+        py::dict d = sweep_dict(p.table);
+        d["repeats"] = p.repeats;
+        d["rho"] = p.rho;
+        return d;
+      },
+      py::arg("width"), py::arg("height"), py::arg("c_center"), py::arg("c_neighbor"), py::arg("coarse_reduction"),
+      "the coarsest level's solve: the 32-level Leja-ordered Chebyshev cycle as a sweep table, its error bound rho "
+      "and the smallest repeat count with rho^repeats <= coarse_reduction");
+  m.attr("MG_COARSEN_ABOVE") = kernels::kMgCoarsenAbove;
+  m.attr("MG_COARSEST_MAX") = kernels::kMgCoarsestMax;
+  m.attr("MG_MAX_SMOOTH") = kernels::kMgMaxSmooth;
   m.def("balanced_starts", &kernels::balanced_starts, py::arg("groups"), py::arg("rows"), py::arg("blocks"),
         py::arg("fill"), py::arg("last_rows") = 0,
         "fill-aware linear starts of the pipeline workgroups' shares (blocks + 1 entries); last_rows > 0: the last "

@@ -20,6 +20,7 @@
 #include "mxs/halo/exchange.hpp"
 #include "mxs/kernels/kernels.hpp"
 #include "mxs/runtime/ipc.hpp"
+#include "mxs/runtime/multigrid_solver.hpp"
 #include "mxs/runtime/pingpong.hpp"
 #include "mxs/runtime/stencil_solver.hpp"
 
@@ -93,6 +94,16 @@ struct SolverHandle {
   DType dt;
   std::unique_ptr<StencilSolver<float>> f;
   std::unique_ptr<StencilSolver<double>> d;
+  template <typename F>
+  auto visit(F&& fn) {
+    return dt == DType::F32 ? fn(*f) : fn(*d);
+  }
+};
+
+struct MultigridHandle {
+  DType dt;
+  std::unique_ptr<MultigridSolver<float>> f;
+  std::unique_ptr<MultigridSolver<double>> d;
   template <typename F>
   auto visit(F&& fn) {
     return dt == DType::F32 ? fn(*f) : fn(*d);
@@ -948,6 +959,181 @@ PYBIND11_MODULE(_mxs_hip, m) {
       .def("fused_periodic", [](SolverHandle& h) { return h.visit([](auto& s) { return s.fused_periodic(); }); })
       .def("overlapped", [](SolverHandle& h) { return h.visit([](auto& s) { return s.overlapped(); }); })
       .def("time_block", [](SolverHandle& h) { return h.visit([](auto& s) { return s.time_block(); }); });
+
+  // ------------------------------------------------------------------ multigrid
+  auto sweep_table = [](const std::vector<double>& center, const std::vector<double>& neighbor,
+                        const std::vector<double>& weight) {
+    if (center.size() != neighbor.size() || center.size() != weight.size() || center.empty() ||
+        int(center.size()) > kernels::kMaxLevels)
+      throw std::invalid_argument("a sweep table takes 1.." + std::to_string(kernels::kMaxLevels) +
+                                  " (center, neighbor, weight) triples");
+    kernels::MgSweepTable t;
+    t.n = int(center.size());
+    for (int l = 0; l < t.n; ++l) {
+      t.center[l] = center[size_t(l)];
+      t.neighbor[l] = neighbor[size_t(l)];
+      t.weight[l] = weight[size_t(l)];
+    }
+    return t;
+  };
+  m.def(
+      "mg_smooth",
+      [sweep_table](std::uintptr_t in, std::uintptr_t out, std::uintptr_t src, const TileGeom& g,
+                    const std::vector<double>& center, const std::vector<double>& neighbor,
+                    const std::vector<double>& weight, const std::string& dt, std::uintptr_t s) {
+        const kernels::MgSweepTable t = sweep_table(center, neighbor, weight);
+        if (parse_dtype(dt) == DType::F32)
+          kernels::mg_smooth<float>(ptr<float>(in), ptr<float>(out), ptr<float>(src), g, t, strm(s));
+        else
+          kernels::mg_smooth<double>(ptr<double>(in), ptr<double>(out), ptr<double>(src), g, t, strm(s));
+      },
+      py::arg("u_in"), py::arg("u_out"), py::arg("src"), py::arg("geom"), py::arg("center"), py::arg("neighbor"),
+      py::arg("weight"), py::arg("dtype") = "f32", py::arg("stream") = 0,
+      "len(center) (1..4) fused sweeps x' = fma(neighbor[l], (n + s) + (w + e), center[l] * c) + T(weight[l]) * g over "
+      "the core of a ring-1 tile, ring cells held; writes the core of u_out only");
+  m.def(
+      "mg_residual_restrict",
+      [](std::uintptr_t u, std::uintptr_t src, const TileGeom& g, std::uintptr_t csrc, const TileGeom& gc, double c0,
+         double c1, const std::string& dt, std::uintptr_t s) {
+        kernels::Stencil5Coeffs c{c0, c1, false, -1.0};
+        if (parse_dtype(dt) == DType::F32)
+          kernels::mg_residual_restrict<float>(ptr<float>(u), ptr<float>(src), g, ptr<float>(csrc), gc, c, strm(s));
+        else
+          kernels::mg_residual_restrict<double>(ptr<double>(u), ptr<double>(src), g, ptr<double>(csrc), gc, c, strm(s));
+      },
+      py::arg("u"), py::arg("src"), py::arg("geom"), py::arg("coarse_src"), py::arg("coarse_geom"),
+      py::arg("c_center") = 0.2, py::arg("c_neighbor") = 0.2, py::arg("dtype") = "f32", py::arg("stream") = 0,
+      "coarse_src core = 4 R ((A u + src) - u): the fine residual and full weighting fused, no fine residual array");
+  m.def(
+      "mg_prolong_add",
+      [](std::uintptr_t e, const TileGeom& gc, std::uintptr_t u, const TileGeom& g, const std::string& dt,
+         std::uintptr_t s) {
+        if (parse_dtype(dt) == DType::F32) kernels::mg_prolong_add<float>(ptr<float>(e), gc, ptr<float>(u), g, strm(s));
+        else kernels::mg_prolong_add<double>(ptr<double>(e), gc, ptr<double>(u), g, strm(s));
+      },
+      py::arg("e"), py::arg("coarse_geom"), py::arg("u"), py::arg("geom"), py::arg("dtype") = "f32",
+      py::arg("stream") = 0, "u core += P e (bilinear, e = 0 outside the coarse core), in place");
+  m.def(
+      "mg_coarse_solve",
+      [sweep_table](std::uintptr_t src, std::uintptr_t e, const TileGeom& g, const std::vector<double>& center,
+                    const std::vector<double>& neighbor, const std::vector<double>& weight, int repeats,
+                    const std::string& dt, std::uintptr_t s) {
+        const kernels::MgSweepTable t = sweep_table(center, neighbor, weight);
+        if (parse_dtype(dt) == DType::F32)
+          kernels::mg_coarse_solve<float>(ptr<float>(src), ptr<float>(e), g, t, repeats, strm(s));
+        else
+          kernels::mg_coarse_solve<double>(ptr<double>(src), ptr<double>(e), g, t, repeats, strm(s));
+      },
+      py::arg("src"), py::arg("e"), py::arg("geom"), py::arg("center"), py::arg("neighbor"), py::arg("weight"),
+      py::arg("repeats"), py::arg("dtype") = "f32", py::arg("stream") = 0,
+      "repeats x len(center) sweeps from e = 0 on a grid of at most 63 x 63 in one workgroup's LDS; writes the core of e");
+  m.def("last_multigrid_dispatch", [] { return std::string(kernels::last_multigrid_dispatch()); },
+        "the kernel the most recent multigrid launcher ran ('' before the first)");
+
+  py::class_<MultigridHandle>(m, "MultigridSolver")
+      .def(py::init([](index_t w, index_t h, const std::string& dt, double c0, double c1, int nu_pre, int nu_post,
+                       double omega, double coarse_reduction, bool graph) {
+             MultigridConfig cfg;
+             cfg.width = w;
+             cfg.height = h;
+             cfg.c_center = c0;
+             cfg.c_neighbor = c1;
+             cfg.nu_pre = nu_pre;
+             cfg.nu_post = nu_post;
+             cfg.smoother_omega = omega;
+             cfg.coarse_reduction = coarse_reduction;
+             cfg.graph = graph;
+             auto h_ = std::make_unique<MultigridHandle>();
+             h_->dt = parse_dtype(dt);
+             if (h_->dt == DType::F32) h_->f = std::make_unique<MultigridSolver<float>>(cfg);
+             else h_->d = std::make_unique<MultigridSolver<double>>(cfg);
+             return h_;
+           }),
+           py::arg("width"), py::arg("height"), py::arg("dtype") = "f64", py::arg("c_center") = 0.2,
+           py::arg("c_neighbor") = 0.2, py::arg("nu_pre") = 2, py::arg("nu_post") = 2, py::arg("smoother_omega") = 0.8,
+           py::arg("coarse_reduction") = 1e-3, py::arg("graph") = true)
+      .def("geom", [](MultigridHandle& h) { return h.visit([](auto& s) { return s.geom(); }); })
+      .def("levels",
+           [](MultigridHandle& h) {
+             std::vector<std::pair<long long, long long>> out;
+             h.visit([&](auto& s) {
+               for (const auto& l : s.levels()) out.emplace_back(l.width, l.height);
+             });
+             return out;
+           })
+      .def(
+          "set_boundary",
+          [](MultigridHandle& h, std::uintptr_t top, std::uintptr_t bottom, std::uintptr_t left, std::uintptr_t right) {
+            h.visit([&](auto& s) {
+              using T = typename std::decay_t<decltype(s)>::value_type;
+              s.set_boundary(ptr<T>(top), ptr<T>(bottom), ptr<T>(left), ptr<T>(right));
+            });
+          },
+          py::arg("top") = 0, py::arg("bottom") = 0, py::arg("left") = 0, py::arg("right") = 0,
+          "device pointers to width (top, bottom) / height (left, right) boundary values; 0 leaves a side as it is")
+      .def(
+          "set_source",
+          [](MultigridHandle& h, std::uintptr_t tile) {
+            h.visit([&](auto& s) {
+              using T = typename std::decay_t<decltype(s)>::value_type;
+              s.set_source(ptr<T>(tile));
+            });
+          },
+          py::arg("tile") = 0, "a device tile of geom() whose core holds g, or 0 (g = 0)")
+      .def("set_field",
+           [](MultigridHandle& h, std::uintptr_t tile) {
+             h.visit([&](auto& s) {
+               using T = typename std::decay_t<decltype(s)>::value_type;
+               s.set_field(ptr<T>(tile));
+             });
+           })
+      .def("field",
+           [](MultigridHandle& h, std::uintptr_t tile) {
+             h.visit([&](auto& s) {
+               using T = typename std::decay_t<decltype(s)>::value_type;
+               s.field(ptr<T>(tile));
+             });
+           })
+      .def("residual",
+           [](MultigridHandle& h) {
+             MultigridResidual r;
+             {
+               py::gil_scoped_release nogil;
+               r = h.visit([](auto& s) { return s.residual(); });
+             }
+             py::dict d;
+             d["linf"] = r.linf;
+             d["l2"] = r.l2;
+             d["cells"] = r.cells;
+             return d;
+           })
+      .def("vcycle", [](MultigridHandle& h, int n) { h.visit([&](auto& s) { s.vcycle(n); }); }, py::arg("n") = 1,
+           py::call_guard<py::gil_scoped_release>())
+      .def(
+          "solve",
+          [](MultigridHandle& h, double tol, int max_cycles, const std::string& norm) {
+            MultigridSolve r;
+            {
+              py::gil_scoped_release nogil;
+              r = h.visit([&](auto& s) { return s.solve(tol, max_cycles, norm); });
+            }
+            py::dict d;
+            d["converged"] = r.converged;
+            d["cycles"] = r.cycles;
+            d["residual"] = r.residual;
+            d["reason"] = r.reason;
+            d["norm"] = r.norm;
+            py::list hist;
+            for (const auto& c : r.history) hist.append(py::make_tuple(c.cycle, c.linf, c.l2));
+            d["history"] = hist;
+            return d;
+          },
+          py::arg("tol"), py::arg("max_cycles") = 50, py::arg("norm") = "l2",
+          "residual() + vcycle(1) until the norm is <= tol, max_cycles ran, the norm is not finite, or no new best "
+          "residual for 3 consecutive cycles ('stalled')")
+      .def("graph_status", [](MultigridHandle& h) { return h.visit([](auto& s) { return s.graph_status(); }); })
+      .def("launches_per_cycle", [](MultigridHandle& h) { return h.visit([](auto& s) { return s.launches_per_cycle(); }); })
+      .def("note", [](MultigridHandle& h) { return h.visit([](auto& s) { return s.note(); }); });
 
   // ------------------------------------------------------------------ ping-pong
   py::enum_<PingPongMode>(m, "PingPongMode")
