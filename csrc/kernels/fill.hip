@@ -50,6 +50,9 @@ template <typename T>
 __global__ __launch_bounds__(kBlock) void fill_random_kernel(T* __restrict__ tile, TileGeom g, index_t gx0,
                                                              index_t gy0, index_t gw, std::uint64_t seed,
                                                              T lo, T span) {
+  // value = lo + round(T(u) * span): the product and the sum stay two rounded
+  // operations (no fma), which is what ops/fill.py's random_values computes.
+#pragma clang fp contract(off)
   const index_t n = g.width * g.height;
   const index_t stride = index_t(gridDim.x) * blockDim.x;
   const index_t base = g.core_offset();
@@ -84,7 +87,8 @@ void fill_random(T* tile, const TileGeom& g, index_t gx0, index_t gy0, index_t g
                  T hi, hipStream_t s) {
   const index_t n = g.width * g.height;
   if (n <= 0) return;
-  fill_random_kernel<T><<<grid_for(n), kBlock, 0, s>>>(tile, g, gx0, gy0, gw, seed, lo, T(hi - lo));
+  const T span = hi - lo;  // formed in T from the rounded ends, as random_values does
+  fill_random_kernel<T><<<grid_for(n), kBlock, 0, s>>>(tile, g, gx0, gy0, gw, seed, lo, span);
   MXS_HIP_CHECK_LAUNCH();
 }
 

@@ -1,12 +1,13 @@
 """Device ops: thin wrappers over the gfx950 HIP kernels (csrc/kernels), with
 exact CPU reference implementations for CPU tensors."""
 from .dot import DotWorkspace, dot  # noqa: F401
+from .exact import box_exact_reference, stencil5_exact_periodic_reference, stencil5_exact_reference  # noqa: F401
 from .fill import fill, fill_random, fill_region, random_values  # noqa: F401
 from .multigrid import (mg_coarse_plan, mg_coarse_solve, mg_coarse_solve_reference, mg_plan_levels,  # noqa: F401
                         mg_prolong_add, mg_prolong_add_reference, mg_prolong_reference, mg_residual_reference,
                         mg_residual_restrict, mg_residual_restrict_reference, mg_restrict_reference, mg_smooth,
                         mg_smooth_reference, mg_smoother_table, multigrid_vcycle_reference)
-from .relaxation import (chebyshev_cycle, jacobi_held_levels_reference, relaxation_spectrum,  # noqa: F401
+from .relaxation import (chebyshev_cycle, fma, jacobi_held_levels_reference, relaxation_spectrum,  # noqa: F401
                          stencil5_tb_held_levels, stencil5_tb_levels)
 from .source import jacobi_source_per_step_reference, source_correction_reference  # noqa: F401
 from .stencil import (HOLD_BOTTOM, HOLD_LEFT, HOLD_RIGHT, HOLD_TOP, box_reference,  # noqa: F401

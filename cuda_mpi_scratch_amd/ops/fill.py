@@ -34,10 +34,11 @@ def random_values(gx0: int, gy0: int, w: int, h: int, global_width: int, seed: i
     hseed = _mix64(np.array([seed], dtype=np.uint64))[0]
     hv = _mix64(key ^ hseed)
     u = (hv >> np.uint64(40)).astype(np.float64) * (1.0 / 16777216.0)
-    t = torch.from_numpy(u)
-    if dtype == torch.float32:
-        return torch.tensor(lo, dtype=torch.float32) + t.float() * torch.tensor(hi - lo, dtype=torch.float32)
-    return lo + t * (hi - lo)
+    # One definition with the kernel: lo + round(T(u) * span), span = T(hi) - T(lo)
+    # formed in T; the product and the sum are two rounded operations.
+    t = torch.from_numpy(u).to(dtype)
+    lo_t, hi_t = torch.tensor(lo, dtype=dtype), torch.tensor(hi, dtype=dtype)
+    return lo_t + t * (hi_t - lo_t)
 
 
 def fill_random(tile: torch.Tensor, geom, gx0: int, gy0: int, global_width: int, seed: int, lo=0.0, hi=1.0,

@@ -142,7 +142,7 @@ def _split(a: torch.Tensor):
     return hi, a - hi
 
 
-def _fma(a, b: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+def fma(a, b: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
     """fma(a, b, c) of the element type, correctly rounded. fp32 goes through
     float64, where a * b is exact; fp64 through error-free products and sums.
     (No overflow or subnormal handling: the fields this is used on are far from
@@ -159,6 +159,9 @@ def _fma(a, b: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
     z = th - c
     tl = (c - (th - z)) + (p - z)  # TwoSum: th + tl == c + p exactly
     return th + _round_to_odd_sum(tl, e)
+
+
+_fma = fma  # the name it had while private
 
 
 def jacobi_held_levels_reference(full: torch.Tensor, center_list, neighbor_list, hold: int = 15,
@@ -184,7 +187,7 @@ def jacobi_held_levels_reference(full: torch.Tensor, center_list, neighbor_list,
         c = u[1:-1, 1:-1]
         sums = (u[:-2, 1:-1] + u[2:, 1:-1]) + (u[1:-1, :-2] + u[1:-1, 2:])
         prod = torch.tensor(c0, dtype=dt) * c
-        new = _fma(c1, sums.contiguous(), prod.contiguous())
+        new = fma(c1, sums.contiguous(), prod.contiguous())
         u = u.clone()
         u[1:-1, 1:-1] = new
         if hold & HOLD_TOP:

@@ -8,7 +8,8 @@ implementations below, which evaluate the same formula in the same order
 
 (the fused multiply-add is emulated in float64 for fp32 tiles: the product of
 two fp32 values is exact in fp64, so only the final rounding differs in rare
-double-rounding cases — tests compare with a 1-ulp tolerance).
+double-rounding cases — tests compare with a 1-ulp tolerance). The bit-exact
+forms of the one-step references live in ``ops/exact.py``.
 """
 from __future__ import annotations
 
