@@ -10,8 +10,9 @@
 //   K2/4/5/8 dot_atomic, dot_partials, reduce_partials, dot_single_pass, dot_racy
 //                                                kernels/dot.hip
 //          stencil5_residual (norms of A u - u)  kernels/residual.hip
-//   K13    level passes with a correction tile, source_axpy (the source term)
-//                                                kernels/stencil_pipe_levels_src_f32/_f64.hip, stencil_levels_src.hip
+//          stencil5_tb_held (fixed-edge frame)   kernels/stencil_held.hip
+//   K13    level passes (Chebyshev cycles), with or without a correction tile; source_axpy (the source term)
+//                                                kernels/stencil_levels.hip, stencil_pipe_levels[_src]_f32/_f64.hip
 //          mg_smooth, mg_residual_restrict, mg_prolong_add, mg_coarse_solve (the multigrid V-cycle)
 //                                                kernels/multigrid.hip
 #pragma once
@@ -244,21 +245,14 @@ void stencil5_tb_held(const T* in, T* out, const TileGeom& g, int steps, index_t
 // with no side held. stencil5_tb_held_levels keeps the contract of
 // stencil5_tb_held ("held_levels"). Both are bitwise equal to t.n single steps
 // with the levels' coefficients.
+// `corr` is nullptr, or a correction tile of geometry g (the source term,
+// docs/ARCHITECTURE.md "Source term"): the pass then ends with out += corr on
+// the rectangle, one rounded add per cell, inside the same launch
+// ("stream_pipe_levels_src" / "held_levels_src"): bitwise the pass without corr
+// followed by that add. Only the rectangle's cells of corr are read, so its
+// ghost ring and padding may hold anything. Kernels: stencil_levels.hip,
+// stencil_pipe_levels[_src]_f32/_f64.hip.
 static_assert(kMaxLevels == kMaxTimeBlockDeep, "a level table holds the deepest time block");
-template <typename T>
-void stencil5_tb_levels(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1,
-                        const LevelTable& t, hipStream_t s);
-template <typename T>
-void stencil5_tb_held_levels(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1,
-                             const LevelTable& t, unsigned hold, hipStream_t s);
-// The same passes with a correction tile (the source term, docs/ARCHITECTURE.md
-// "Source term"): `corr` is a tile of geometry g, and the pass ends with
-// out += corr on the rectangle, one rounded add per cell, inside the same
-// launch ("stream_pipe_levels_src" / "held_levels_src"): bitwise the pass
-// without corr followed by that add. Only the rectangle's cells of corr are
-// read, so its ghost ring and padding may hold anything. corr == nullptr runs
-// exactly the launch above. Kernels: stencil_pipe_levels_src_f32/_f64.hip,
-// stencil_levels_src.hip.
 template <typename T>
 void stencil5_tb_levels(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1,
                         const LevelTable& t, const T* corr, hipStream_t s);

@@ -47,6 +47,7 @@
 #include "mxs/runtime/hip_utils.hpp"
 
 #include "stencil_device.hpp"
+#include "stencil_held.hpp"
 #include "stencil_pipe.hpp"
 
 namespace mxs {
@@ -298,22 +299,13 @@ template <typename T>
 void stencil5_tb(const T* in, T* out, const TileGeom& g, int steps, index_t x0, index_t x1, index_t y0, index_t y1,
                  Stencil5Coeffs c, bool wrap, hipStream_t s, StencilVariant v) {
   if (x1 <= x0 || y1 <= y0) return;
-  constexpr int N = Vec16<T>::N;
-  MXS_CHECK(x0 >= 0 && y0 >= 0 && x1 <= g.width && y1 <= g.height, "stencil5_tb: rect out of the core");
+  check_block_rect<T>("stencil5_tb", g, steps, x0, x1, y0, y1, /*ring=*/!wrap);
   MXS_CHECK(stencil5_deep_supported<T>(steps, x0, x1),
             "stencil5_tb: " << steps << "-step blocks need fp32 and a column range of whole vectors (got "
                             << sizeof(T) * 8 << "-bit, [" << x0 << ", " << x1 << "))");
-  MXS_CHECK(x0 % N == 0, "stencil5_tb: x0 must be a multiple of the vector width");
-  MXS_CHECK((g.pitch % N) == 0 && ((g.x_origin + g.halo_x) % N) == 0, "stencil5_tb needs a TileGeom::aligned layout");
-  const int sa = ((steps + N - 1) / N) * N;
   if (wrap) {
-    MXS_CHECK(g.width % N == 0, "stencil5_tb wrap: width must be a multiple of the vector width");
+    MXS_CHECK(g.width % Vec16<T>::N == 0, "stencil5_tb wrap: width must be a multiple of the vector width");
     MXS_CHECK(g.height >= steps, "stencil5_tb wrap: tile height " << g.height << " < time block " << steps);
-  } else {
-    MXS_CHECK(g.halo_x >= steps && g.halo_y >= steps,
-              "stencil5_tb: ghost ring (" << g.halo_x << ") shallower than the time block (" << steps << ")");
-    MXS_CHECK(g.x_origin + g.halo_x >= sa && g.pitch >= g.x_origin + g.halo_x + ((g.width + N - 1) / N) * N + sa,
-              "stencil5_tb: row padding too small for the x apron");
   }
   const T c0 = T(c.center), c1 = T(c.neighbor);
   // Fast forms only inside their bounds (fast_form_verdict: coefficients, c1^S

@@ -64,7 +64,7 @@ __device__ __forceinline__ CoeffPair<T> level_coeff(const LevelPairs<T, S>& c, i
   return c.v[l];
 }
 // A level source may also carry a correction tile that the pipeline adds to
-// every stored cell (the source term, stencil_pipe_levels_src.hpp). The
+// every stored cell (the source term, stencil_pipe_levels.hpp). The
 // pipeline asks CoeffCorr<C>::value at compile time, so the kernels of every
 // other coefficient source keep their instructions.
 template <typename C>

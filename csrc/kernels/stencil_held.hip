@@ -23,29 +23,6 @@ void note_launch(const char* kernel, const PipeForm& form = {}, bool split = fal
 namespace {
 using namespace detail;
 
-template <typename T, int S, int TW, int TH>
-void launch_held_tile(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1, T c0, T c1,
-                      unsigned hold, hipStream_t s) {
-  const size_t lds = held_lds_bytes<T, S, TW, TH>();
-  const dim3 grid(unsigned((x1 - x0 + TW - 1) / TW), unsigned((y1 - y0 + TH - 1) / TH));
-  stencil5_tb_held_kernel<T, S, TW, TH><<<grid, 256, lds, s>>>(in, out, g.pitch, g.core_offset(), g.width, g.height, x0,
-                                                              x1, y0, y1, c0, c1, hold);
-}
-
-// Tile shape by rectangle shape, as launch_tb does for the overlap schedule's
-// thin strips: a column strip (the left / right frame: S columns rounded to
-// whole vectors) gets the tall narrow tile, a row strip (the top / bottom
-// frame: S rows) the wide flat one, anything else the general tile.
-template <typename T, int S>
-void launch_held(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1, T c0, T c1,
-                 unsigned hold, hipStream_t s) {
-  using Sh = HeldShape<T, S>;
-  if (x1 - x0 <= Sh::NW + Sh::NW / 4)
-    return launch_held_tile<T, S, Sh::NW, Sh::NH>(in, out, g, x0, x1, y0, y1, c0, c1, hold, s);
-  if (y1 - y0 <= Sh::FH) return launch_held_tile<T, S, Sh::FW, Sh::FH>(in, out, g, x0, x1, y0, y1, c0, c1, hold, s);
-  launch_held_tile<T, S, Sh::GW, Sh::GH>(in, out, g, x0, x1, y0, y1, c0, c1, hold, s);
-}
-
 template <typename T>
 constexpr int held_max_steps() {
   return sizeof(T) == 4 ? kMaxTimeBlockDeep : kMaxTimeBlock;
@@ -67,20 +44,11 @@ template <typename T>
 void stencil5_tb_held(const T* in, T* out, const TileGeom& g, int steps, index_t x0, index_t x1, index_t y0, index_t y1,
                       Stencil5Coeffs c, unsigned hold, hipStream_t s) {
   if (x1 <= x0 || y1 <= y0) return;
-  constexpr int N = Vec16<T>::N;
   MXS_CHECK(steps >= 1 && steps <= held_max_steps<T>(),
             "stencil5_tb_held: steps must be in [1, " << held_max_steps<T>() << "], got " << steps);
-  MXS_CHECK(x0 >= 0 && y0 >= 0 && x1 <= g.width && y1 <= g.height, "stencil5_tb_held: rect out of the core");
-  MXS_CHECK(x0 % N == 0, "stencil5_tb_held: x0 must be a multiple of the vector width");
+  check_block_rect<T>("stencil5_tb_held", g, steps, x0, x1, y0, y1);
   MXS_CHECK((hold & ~unsigned(kHoldTop | kHoldBottom | kHoldLeft | kHoldRight)) == 0,
             "stencil5_tb_held: hold takes the HoldSide bits only, got " << hold);
-  MXS_CHECK((g.pitch % N) == 0 && ((g.x_origin + g.halo_x) % N) == 0,
-            "stencil5_tb_held needs a TileGeom::aligned layout");
-  const int sa = ((steps + N - 1) / N) * N;
-  MXS_CHECK(g.halo_x >= steps && g.halo_y >= steps,
-            "stencil5_tb_held: ghost ring (" << g.halo_x << ") shallower than the time block (" << steps << ")");
-  MXS_CHECK(g.x_origin + g.halo_x >= sa && g.pitch >= g.x_origin + g.halo_x + ((g.width + N - 1) / N) * N + sa,
-            "stencil5_tb_held: row padding too small for the x apron");
   dispatch_held<T>(steps, in, out, g, x0, x1, y0, y1, T(c.center), T(c.neighbor), hold, s);
   note_launch("tb_held");
   MXS_HIP_CHECK_LAUNCH();

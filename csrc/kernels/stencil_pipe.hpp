@@ -96,24 +96,18 @@ void pipe_starts(index_t groups, index_t rows, int blocks, index_t fill, PipeSha
 // MXS_PIPE_BALANCED=0: equal row shares (the round-2 rule), for comparison.
 bool pipe_balanced();
 
-template <typename T, int S, bool WRAP, EvalForm EF, int JS0, int LAG1>
-void launch_pipe_form(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1, T c0,
-                      T c1, const PipeChoice& ch, hipStream_t s) {
-  static_assert(EF != EvalForm::Scaled || JS0 > 0, "the scaled form runs the joint pipeline");
-  static_assert(JS0 > 0 || pipe_owg(kPerStrip<T, S, EF>) == kWavesPerBlock * StripShape<T, S, true>::OW,
-                "pipe_form.hpp's per-strip group is the kernel's");
-  const index_t rows = y1 - y0, groups = pipe_groups(ch.form, x1 - x0);
+// The shares of one pipeline pass in form `ch` over cols x rows on `blocks`
+// workgroups, for the uniform and the level-table launchers alike. may_split:
+// whether the kernel about to be launched can split its narrow last group
+// (pipe_split_form).
+template <typename T>
+PipeShares pipe_pass_shares(const char* who, const TileGeom& g, const PipeChoice& ch, index_t cols, index_t rows,
+                            int blocks, bool may_split) {
+  const index_t groups = pipe_groups(ch.form, cols);
   // The same lengths in the share, the fill-aware starts and the kernel's own
   // `total`: the narrow last group counts split_half rows when it is split.
-  const index_t split_half = pipe_split_half(ch, x1 - x0, rows);
-  MXS_CHECK(split_half == 0 || (pipe_split_form<T, JS0, S - JS0, kWavesPerBlock, (JS0 > 0), LAG1>()),
-            "stencil5_tb: this pipeline form does not split its last group");
-  // One 512-thread workgroup per CU: the occupancy API decides, asked about
-  // the descending-order sum / per-step kernel of the same windows.
-  const int blocks = resident_workgroups(
-      reinterpret_cast<const void*>(
-          pipe_kernel<T, S, WRAP, eval_sum(EF) ? EvalForm::Sum : EvalForm::PerStep, JS0, 0>()),
-      2 * kBlock, 1);
+  const index_t split_half = pipe_split_half(ch, cols, rows);
+  MXS_CHECK(split_half == 0 || may_split, who << ": this pipeline form does not split its last group");
   const index_t total = split_half > 0 ? (groups - 1) * rows + split_half : groups * rows;
   PipeShares shares = PipeShares::equal((total + blocks - 1) / blocks);  // rows per workgroup of the linear space
   shares.split_half = split_half;
@@ -122,8 +116,26 @@ void launch_pipe_form(const T* in, T* out, const TileGeom& g, index_t x0, index_
   // Shares longer than kMaxChunkBytes are walked in pieces inside the kernel;
   // a piece must still hold a useful number of rows.
   MXS_CHECK(chunk_rows_fit(g.pitch, sizeof(T)),
-            "stencil5_tb: rows of " << g.pitch * index_t(sizeof(T)) << " bytes leave fewer than " << kMinChunkRows
-                                    << " rows per pipeline chunk (buffer-descriptor stores)");
+            who << ": rows of " << g.pitch * index_t(sizeof(T)) << " bytes leave fewer than " << kMinChunkRows
+                << " rows per pipeline chunk (buffer-descriptor stores)");
+  return shares;
+}
+
+template <typename T, int S, bool WRAP, EvalForm EF, int JS0, int LAG1>
+void launch_pipe_form(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1, T c0,
+                      T c1, const PipeChoice& ch, hipStream_t s) {
+  static_assert(EF != EvalForm::Scaled || JS0 > 0, "the scaled form runs the joint pipeline");
+  static_assert(JS0 > 0 || pipe_owg(kPerStrip<T, S, EF>) == kWavesPerBlock * StripShape<T, S, true>::OW,
+                "pipe_form.hpp's per-strip group is the kernel's");
+  // One 512-thread workgroup per CU: the occupancy API decides, asked about
+  // the descending-order sum / per-step kernel of the same windows.
+  const int blocks = resident_workgroups(
+      reinterpret_cast<const void*>(
+          pipe_kernel<T, S, WRAP, eval_sum(EF) ? EvalForm::Sum : EvalForm::PerStep, JS0, 0>()),
+      2 * kBlock, 1);
+  const PipeShares shares =
+      pipe_pass_shares<T>("stencil5_tb", g, ch, x1 - x0, y1 - y0, blocks,
+                          pipe_split_form<T, JS0, S - JS0, kWavesPerBlock, (JS0 > 0), LAG1>());
   const KernelCoeffs<T> k = kernel_coeffs(EF, c0, c1, S);
   constexpr bool kBlockPrio = pipe_block_prio_form<T, JS0, S - JS0, (JS0 > 0), LAG1, eval_sum(EF)>();
   MXS_CHECK(!ch.block_prio || kBlockPrio, "stencil5_tb: this pipeline form has no block-priority kernel");
@@ -138,7 +150,7 @@ void launch_pipe_form(const T* in, T* out, const TileGeom& g, index_t x0, index_
     launch(pipe_kernel<T, S, WRAP, EF, JS0, LAG1>());
   }
   note_launch(EF == EvalForm::Scaled ? "stream_pipe_scaled" : EF == EvalForm::Sum ? "stream_pipe_sum" : "stream_pipe",
-              ch.form, split_half > 0, ch.block_prio);
+              ch.form, shares.split_half > 0, ch.block_prio);
 }
 
 template <typename T, int S, bool WRAP, EvalForm EF>

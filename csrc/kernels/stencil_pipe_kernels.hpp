@@ -20,6 +20,28 @@
 // jac_vec) left every kernel's opcode sequence and register counts alone.
 // Whoever tries again proves it with scripts/isa_same.py and a GPU measurement
 // of every pipeline form.
+//
+// SHARED OVER THE COEFFICIENT SOURCE. None of the above forbids one kernel for
+// several coefficient sources: the source is a kernel argument read through
+// level_coeff (stencil_bodies.hpp), the window arrays stay where they are. Like
+// pipe_chunk, two kernels are templates over it:
+//   * the held tile (stencil_held.hpp), over T or LevelArray<T, S> and an
+//     optional correction tile: 144 uniform, 12 level and 12 level + corr
+//     kernels;
+//   * the share walk of the level pipeline (stencil_pipe_levels.hpp), over
+//     LevelPairs<T, S> or LevelPairsSrc<T, S>: 11 + 11 kernels.
+// Each is, line for line, the kernel that was written out per source before
+// (isa_same.py --pair, profiles/held_unify/isa_same.txt). Two spellings of the
+// optional correction pointer were not harmless:
+//   * a trailing argument of an empty "no corr" struct type instead of the
+//     empty parameter pack: .amdhsa_kernarg_size grows by 4 on the 156 kernels
+//     without a correction;
+//   * the pack's pointer without __restrict__: the scalar loads of the 12 corr
+//     kernels change.
+// The uniform stencil5_stream_pipe_kernel keeps its own share walk (one
+// __forceinline__ body for it and the level kernel reordered the scalar
+// prologue of all 162 one-launch kernels, docs/PERF.md), and stencil5_tb1_kernel
+// its own write-out (above).
 #pragma once
 
 #include "stencil_stream.hpp"

@@ -3,9 +3,22 @@
 // the per-step form, ghost-ring tiles only (no wrap), with one coefficient pair
 // per level instead of two uniforms. Same forms as the uniform per-step pass
 // (pipe_form_for(..., EvalForm::PerStep, ...), with_pipe_form), same shares,
-// same VALU work per cell. Instantiated in stencil_pipe_levels_f32.hip (S = 20,
-// 24) and stencil_pipe_levels_f64.hip (S = 12, 16), so the translation units of
-// the uniform kernels compile as before.
+// same VALU work per cell.
+//
+// One kernel and one launcher for both level sources C (stencil_bodies.hpp):
+// LevelPairs<T, S>, the table alone ("stream_pipe_levels"), and
+// LevelPairsSrc<T, S>, the table and `corr`, a tile of the pass's geometry (the
+// source term, docs/ARCHITECTURE.md "Source term": "stream_pipe_levels_src").
+// With the latter, stage 1 of pipe_chunk loads a lane's 4 cells of `corr` at
+// the store's own offset when it starts a row's level chain and adds them to the
+// row it stores (CoeffCorr): one more read stream over the core and one rounded
+// add per cell, every level untouched. Only cells that are stored are read from
+// `corr` (a dropped lane or row is past the descriptor's range and loads 0), so
+// its ghost ring and padding never enter.
+// Instantiated in stencil_pipe_levels_f32.hip (S = 20, 24) and
+// stencil_pipe_levels_f64.hip (S = 12, 16), with `corr` in
+// stencil_pipe_levels_src_f32.hip and stencil_pipe_levels_src_f64.hip, so the
+// translation units of the uniform kernels compile as before.
 #pragma once
 
 #include "mxs/kernels/relaxation.hpp"
@@ -73,13 +86,12 @@ struct LevelBody<double> {
 
 // The table rides in the kernel arguments (2 S scalars behind the 2 KB of
 // PipeShares): every level's pair is a scalar load, nothing is stored.
-template <int S0, int S1, int PF, typename T, bool JOINT, int LAG1>
+template <int S0, int S1, int PF, typename T, bool JOINT, int LAG1, typename C>
 __global__ __launch_bounds__(2 * kWavesPerBlock * kWaveSize) void stencil5_stream_pipe_levels_kernel(
     const T* __restrict__ in, T* __restrict__ out, index_t pitch, index_t core_off, index_t W, index_t H,
-    index_t x_begin, index_t x_end, index_t y_begin, index_t y_end, const PipeShares shares,
-    const LevelPairs<T, S0 + S1> cs) {
+    index_t x_begin, index_t x_end, index_t y_begin, index_t y_end, const PipeShares shares, const C cs) {
   // The share walk of stencil5_stream_pipe_kernel (no wrap, no tuning switches),
-  // written out again: see the note at the top of stencil_pipe_kernels.hpp.
+  // over a level source: see the note at the top of stencil_pipe_kernels.hpp.
   constexpr int G = kWavesPerBlock;
   using P = PipeShape<S0, S1, PF>;
   using B = typename LevelBody<T>::type;
@@ -139,62 +151,40 @@ __global__ __launch_bounds__(2 * kWavesPerBlock * kWaveSize) void stencil5_strea
   }
 }
 
-// The table's doubles rounded to T once, here on the host.
-template <typename T, int S>
-void level_arrays(const LevelTable& t, LevelArray<T, S>* c0, LevelArray<T, S>* c1) {
-  for (int l = 0; l < S; ++l) {
-    c0->v[l] = T(t.center[l]);
-    c1->v[l] = T(t.neighbor[l]);
-  }
-}
-template <typename T, int S>
-LevelPairs<T, S> level_pairs(const LevelTable& t) {
-  LevelPairs<T, S> p;
-  for (int l = 0; l < S; ++l) p.v[l] = CoeffPair<T>{T(t.center[l]), T(t.neighbor[l])};
-  return p;
-}
-
-template <typename T, int S, int JS0, int LAG1>
+// `cs`: the filled level source; `name`: the dispatch name of its launches.
+template <typename T, int S, int JS0, int LAG1, typename C>
 void launch_pipe_levels_form(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1,
-                             const LevelTable& t, const PipeChoice& ch, hipStream_t s) {
+                             const C& cs, const char* name, const PipeChoice& ch, hipStream_t s) {
   constexpr PipeForm P = kPerStrip<T, S, EvalForm::PerStep>;
   constexpr int S0 = JS0 > 0 ? JS0 : P.s0;
-  constexpr auto kernel = stencil5_stream_pipe_levels_kernel<S0, S - S0, P.pf, T, (JS0 > 0), (JS0 > 0 ? LAG1 : 0)>;
-  // Shares exactly as launch_pipe_form computes them for the uniform pass.
-  const index_t rows = y1 - y0, groups = pipe_groups(ch.form, x1 - x0);
-  const index_t split_half = pipe_split_half(ch, x1 - x0, rows);
-  MXS_CHECK(split_half == 0 || (pipe_split_form<T, JS0, S - JS0, kWavesPerBlock, (JS0 > 0), LAG1>()),
-            "stencil5_tb_levels: this pipeline form does not split its last group");
+  constexpr auto kernel = stencil5_stream_pipe_levels_kernel<S0, S - S0, P.pf, T, (JS0 > 0), (JS0 > 0 ? LAG1 : 0), C>;
   const int blocks = resident_workgroups(reinterpret_cast<const void*>(kernel), 2 * kBlock, 1);
-  const index_t total = split_half > 0 ? (groups - 1) * rows + split_half : groups * rows;
-  PipeShares shares = PipeShares::equal((total + blocks - 1) / blocks);
-  shares.split_half = split_half;
-  if (pipe_balanced() && blocks <= kMaxShareBlocks)
-    pipe_starts(groups, rows, blocks, pipe_fill_rows(ch.form), &shares, split_half);
-  MXS_CHECK(chunk_rows_fit(g.pitch, sizeof(T)),
-            "stencil5_tb_levels: rows of " << g.pitch * index_t(sizeof(T)) << " bytes leave fewer than " << kMinChunkRows
-                                           << " rows per pipeline chunk (buffer-descriptor stores)");
-  kernel<<<blocks, 2 * kBlock, 0, s>>>(in, out, g.pitch, g.core_offset(), g.width, g.height, x0, x1, y0, y1, shares,
-                                       level_pairs<T, S>(t));
-  note_launch("stream_pipe_levels", ch.form, split_half > 0, false);
+  const PipeShares shares =
+      pipe_pass_shares<T>("stencil5_tb_levels", g, ch, x1 - x0, y1 - y0, blocks,
+                          pipe_split_form<T, JS0, S - JS0, kWavesPerBlock, (JS0 > 0), LAG1>());
+  kernel<<<blocks, 2 * kBlock, 0, s>>>(in, out, g.pitch, g.core_offset(), g.width, g.height, x0, x1, y0, y1, shares, cs);
+  note_launch(name, ch.form, shares.split_half > 0, false);
 }
 
 // One S-level pass over [x0, x1) x [y0, y1) of a ghost-ring tile in the form
 // the uniform per-step pass of these columns takes.
-template <typename T, int S>
+template <typename T, int S, typename C>
 void launch_pipe_levels_impl(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1,
-                             const LevelTable& t, hipStream_t s) {
+                             const C& cs, const char* name, hipStream_t s) {
   const PipeChoice ch = pipe_form_for(int(sizeof(T)), S, EvalForm::PerStep, x1 - x0, pipe_switches());
   with_pipe_form<T, S, EvalForm::PerStep>(ch, [&](auto tag) {
     using K = decltype(tag);
-    launch_pipe_levels_form<T, S, K::JS0, K::LAG1>(in, out, g, x0, x1, y0, y1, t, ch, s);
+    launch_pipe_levels_form<T, S, K::JS0, K::LAG1>(in, out, g, x0, x1, y0, y1, cs, name, ch, s);
   });
 }
 
-// Explicitly instantiated in the level-pipeline TUs.
-template <typename T, int S>
+// Explicitly instantiated in the four level-pipeline TUs, each for its source.
+template <typename T, int S, typename C>
 void launch_pipe_levels(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1,
-                        const LevelTable& t, hipStream_t s);
+                        const C& cs, const char* name, hipStream_t s);
+#define MXS_INST_PIPE_LEVELS(T, S, C)                                                                                 \
+  template void launch_pipe_levels<T, S, C<T, S>>(const T*, T*, const TileGeom&, index_t, index_t, index_t, index_t, \
+                                                  const C<T, S>&, const char*, hipStream_t)
 
 }  // namespace detail
 }  // namespace kernels

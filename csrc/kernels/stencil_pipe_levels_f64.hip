@@ -6,16 +6,14 @@ namespace mxs {
 namespace kernels {
 namespace detail {
 
-template <typename T, int S>
+template <typename T, int S, typename C>
 void launch_pipe_levels(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1,
-                        const LevelTable& t, hipStream_t s) {
-  launch_pipe_levels_impl<T, S>(in, out, g, x0, x1, y0, y1, t, s);
+                        const C& cs, const char* name, hipStream_t s) {
+  launch_pipe_levels_impl<T, S, C>(in, out, g, x0, x1, y0, y1, cs, name, s);
 }
 
-template void launch_pipe_levels<double, 12>(const double*, double*, const TileGeom&, index_t, index_t, index_t, index_t,
-                                             const LevelTable&, hipStream_t);
-template void launch_pipe_levels<double, 16>(const double*, double*, const TileGeom&, index_t, index_t, index_t, index_t,
-                                             const LevelTable&, hipStream_t);
+MXS_INST_PIPE_LEVELS(double, 12, LevelPairs);
+MXS_INST_PIPE_LEVELS(double, 16, LevelPairs);
 
 }  // namespace detail
 }  // namespace kernels

@@ -1,21 +1,19 @@
 // Level-table pipeline with a correction tile, fp64 S = 12 and 16 (wide-lane
-// body): the source-term passes (stencil_pipe_levels_src.hpp).
-#include "stencil_pipe_levels_src.hpp"
+// body): the source-term passes (stencil_pipe_levels.hpp, LevelPairsSrc).
+#include "stencil_pipe_levels.hpp"
 
 namespace mxs {
 namespace kernels {
 namespace detail {
 
-template <typename T, int S>
-void launch_pipe_levels_src(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1,
-                            const LevelTable& t, const T* corr, hipStream_t s) {
-  launch_pipe_levels_src_impl<T, S>(in, out, g, x0, x1, y0, y1, t, corr, s);
+template <typename T, int S, typename C>
+void launch_pipe_levels(const T* in, T* out, const TileGeom& g, index_t x0, index_t x1, index_t y0, index_t y1,
+                        const C& cs, const char* name, hipStream_t s) {
+  launch_pipe_levels_impl<T, S, C>(in, out, g, x0, x1, y0, y1, cs, name, s);
 }
 
-template void launch_pipe_levels_src<double, 12>(const double*, double*, const TileGeom&, index_t, index_t, index_t,
-                                                 index_t, const LevelTable&, const double*, hipStream_t);
-template void launch_pipe_levels_src<double, 16>(const double*, double*, const TileGeom&, index_t, index_t, index_t,
-                                                 index_t, const LevelTable&, const double*, hipStream_t);
+MXS_INST_PIPE_LEVELS(double, 12, LevelPairsSrc);
+MXS_INST_PIPE_LEVELS(double, 16, LevelPairsSrc);
 
 }  // namespace detail
 }  // namespace kernels

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
 """Are the kernels of two builds the same, instruction for instruction?
 
-    python scripts/isa_same.py DIR_A DIR_B [--allow-operand-order SUBSTRING ...]
+    python scripts/isa_same.py DIR_A DIR_B [--allow-operand-order SUBSTRING ...] [--pair REGEX ...]
 
 Each directory holds hipcc `-S` gfx950 assembly files with the same names, one
 per translation unit of the stencil kernels, made with the flags CMakeLists.txt
 gives those files:
 
-    for t in stencil stencil_pipe_f32 stencil_pipe_f64 stencil_pipe_chunks stencil_held; do
+    for t in stencil stencil_pipe_f32 stencil_pipe_f64 stencil_pipe_chunks stencil_held stencil_levels \\
+             stencil_pipe_levels_f32 stencil_pipe_levels_f64 stencil_pipe_levels_src_f32 stencil_pipe_levels_src_f64; do
       hipcc --offload-arch=gfx950 --cuda-device-only -S -O3 -munsafe-fp-atomics -fno-slp-vectorize \\
             -std=c++17 -Icsrc/include -Wno-unused-result csrc/kernels/$t.hip -o DIR/$t.s &
     done; wait
@@ -23,6 +24,13 @@ function index in local labels are dropped; every kernel is then
                    plain commutative VALU operation (kCommutative) with its two
                    source operands exchanged: bitwise harmless;
     different      anything else, a symbol on one side only included.
+
+A build that renames kernels (other template arguments, another namespace)
+pairs them with --pair REGEX, repeatable: a kernel whose demangled name (its
+symbol, if no demangler is found) matches REGEX is keyed by the tuple of the
+regex's groups instead of by its symbol, and its own symbol is replaced by a
+placeholder inside its body. Two kernels of one file and side under one key are
+an error (exit status 2), never a pair.
 
 One summary line per file, one line per kernel that is not identical (both
 VGPR counts, the first opcode-count differences). Exit status 0 only if every
@@ -100,18 +108,40 @@ def demangled(symbols):
     return {s: s for s in symbols}
 
 
-def compare_file(name, path_a, path_b, allow):
+class Ambiguous(Exception):
+    pass
+
+
+def keyed(side, kern, names, pairs):
+    """{key: (symbol, body)}: the key is the symbol, or for a kernel that a
+    --pair regex matches the tuple of its groups (its body then names itself by
+    a placeholder)."""
+    out = {}
+    for sym, body in kern.items():
+        m = next(filter(None, (p.search(names[sym]) for p in pairs)), None)
+        key = m.groups() if m else sym
+        if m:
+            body = [t.replace(sym, "<kernel>") for t in body]
+        if key in out:
+            raise Ambiguous(f"{side}: --pair gives {names[out[key][0]]} and {names[sym]} the same key {key}")
+        out[key] = (sym, body)
+    return out
+
+
+def compare_file(name, path_a, path_b, allow, pairs=()):
     """Prints the file's lines; returns the number of kernels that fail."""
     ka, kb = kernels(path_a), kernels(path_b)
     names = demangled(sorted(set(ka) | set(kb)))
+    ka, kb = keyed(path_a, ka, names, pairs), keyed(path_b, kb, names, pairs)
     count, bad, notes = collections.Counter(), 0, []
-    for sym in sorted(set(ka) | set(kb)):
-        if sym not in ka or sym not in kb:
-            count["only in A" if sym in ka else "only in B"] += 1
+    for key in sorted(set(ka) | set(kb), key=str):
+        sym = (ka.get(key) or kb[key])[0]
+        if key not in ka or key not in kb:
+            count["only in A" if key in ka else "only in B"] += 1
             bad += 1
-            notes.append(f"  {'only in A' if sym in ka else 'only in B'}: {names[sym]}")
+            notes.append(f"  {'only in A' if key in ka else 'only in B'}: {names[sym]}")
             continue
-        a, b = ka[sym], kb[sym]
+        a, b = ka[key][1], kb[key][1]
         kind = classify(a, b)
         count[kind] += 1
         if kind == "identical":
@@ -133,10 +163,13 @@ def compare_file(name, path_a, path_b, allow):
 
 
 def main(argv):
-    allow, dirs, i = [], [], 0
+    allow, pairs, dirs, i = [], [], [], 0
     while i < len(argv):
         if argv[i] == "--allow-operand-order" and i + 1 < len(argv):
             allow.append(argv[i + 1])
+            i += 2
+        elif argv[i] == "--pair" and i + 1 < len(argv):
+            pairs.append(re.compile(argv[i + 1]))
             i += 2
         else:
             dirs.append(argv[i])
@@ -152,7 +185,11 @@ def main(argv):
             print(f"{f}: only in {dirs[0] if f in fa else dirs[1]}")
             bad += 1
             continue
-        bad += compare_file(f, os.path.join(dirs[0], f), os.path.join(dirs[1], f), allow)
+        try:
+            bad += compare_file(f, os.path.join(dirs[0], f), os.path.join(dirs[1], f), allow, pairs)
+        except Ambiguous as e:
+            print(e)
+            return 2
     if not fa | fb:
         print("no .s files")
         bad += 1

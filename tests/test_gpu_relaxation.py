@@ -138,6 +138,37 @@ def test_uniform_table_reproduces_the_per_step_kernels(gpu, w, h, S, dtype):
         assert torch.equal(a, b), f"a uniform level table differs from the per-step stencil5_tb_held (hold {hold})"
 
 
+# The held tile is one body for its three coefficient sources (uniform pair,
+# level table, level table + correction tile). Widths that are no whole number
+# of vectors (70 fp32, 35 fp64) put a ragged last vector beside the held right
+# side; the three rectangles take the general, the narrow and the flat tile.
+@pytest.mark.parametrize("shape", ["general", "narrow", "flat"])
+@pytest.mark.parametrize("w,S,dtype", [(70, 20, F32), (35, 12, F64)])
+def test_held_tile_is_one_body_for_its_three_sources(gpu, w, S, dtype, shape):
+    h, c0, c1 = 40, 0.5, 0.125
+    g, _, src, _, _ = _tile(gpu, w, h, S, dtype)
+    N = 16 // src.element_size()
+    x0, x1, y0, y1 = {"general": (0, w, 0, h), "narrow": (0, N * ((S + N - 1) // N), 0, h), "flat": (0, w, 0, S)}[shape]
+    gen = torch.Generator(device="cpu").manual_seed(7 * w + S)
+    corr = (torch.rand(g.alloc_elems(), generator=gen, dtype=torch.float64) * 2 - 1).to(dtype).to(gpu)
+    for hold in (0, 15, ops.HOLD_RIGHT):
+        uni, lev, got = (torch.full_like(src, -3.0) for _ in range(3))
+        ops.stencil5_tb_held(src, uni, g, S, x0, x1, y0, y1, c0, c1, hold)
+        assert hip().last_stencil_dispatch() == "tb_held"
+        ops.stencil5_tb_held_levels(src, lev, g, x0, x1, y0, y1, [c0] * S, [c1] * S, hold)
+        assert hip().last_stencil_dispatch() == "held_levels"
+        ops.stencil5_tb_held_levels(src, got, g, x0, x1, y0, y1, [c0] * S, [c1] * S, hold, corr=corr)
+        assert hip().last_stencil_dispatch() == "held_levels_src"
+        torch.cuda.synchronize()
+        assert torch.equal(uni, lev), f"{shape} hold {hold}: the uniform table differs from stencil5_tb_held"
+        want = lev.clone()
+        _core(want, g)[y0:y1, x0:x1] += _core(corr, g)[y0:y1, x0:x1]  # one rounded add in the element type
+        assert torch.equal(got, want), f"{shape} hold {hold}: with corr, not the pass plus corr on the rectangle"
+        outside = torch.ones(g.alloc_elems(), dtype=torch.bool, device=gpu)
+        _core(outside, g)[y0:y1, x0:x1] = False
+        assert (got[outside] == -3.0).all() and (_core(got, g)[y0:y1, x0:x1] != -3.0).all()
+
+
 def test_level_depths_without_kernels_are_errors(gpu):
     g, _, src, _, _ = _tile(gpu, 72, 40, 20, F32)
     dst = torch.empty_like(src)

@@ -1,6 +1,7 @@
-"""scripts/isa_same.py on three pairs of tiny hand-written assembly texts (two
+"""scripts/isa_same.py on pairs of tiny hand-written assembly texts (two
 kernels each): equal up to comments and the cuid symbol, one swapped
-v_add_f32_e32, one extra v_mov_b32. No GPU and no compiler."""
+v_add_f32_e32, one extra v_mov_b32, one kernel renamed (--pair). No GPU and no
+compiler."""
 import importlib.util
 import os
 
@@ -89,6 +90,33 @@ def test_extra_instruction_is_different(tmp_path, capsys):
     assert status == 1
     assert "1 identical, 0 operand-order, 1 different" in out and "v_mov_b32_e32 0 -> 1" in out
     assert run(tmp_path, capsys, EXTRA, "--allow-operand-order", "axpy")[0] == 1
+
+
+# A build that renames one kernel (axpy gains a template argument): --pair keys
+# it by the regex's groups and hides its own symbol inside its body.
+RENAMED = BASE.replace("_Z4axpyPf", "_Z4axpyIfEvPT_")
+RENAMED_EXTRA = EXTRA.replace("_Z4axpyPf", "_Z4axpyIfEvPT_")
+
+
+def test_a_renamed_kernel_pairs_only_with_the_option(tmp_path, capsys):
+    status, out = run(tmp_path, capsys, RENAMED)
+    assert status == 1
+    assert "1 identical, 0 operand-order, 0 different, 1 only in A, 1 only in B" in out
+    status, out = run(tmp_path, capsys, RENAMED, "--pair", "(axpy)")
+    assert status == 0
+    assert out.splitlines() == ["unit.s: 2 kernels: 2 identical, 0 operand-order, 0 different, 0 only in A, 0 only in B"]
+
+
+def test_an_ambiguous_pair_is_an_error(tmp_path, capsys):
+    status, out = run(tmp_path, capsys, RENAMED, "--pair", "(p)")  # axpy and copy both key as ("p",)
+    assert status == 2 and "the same key" in out
+    assert run(tmp_path, capsys, RENAMED, "--pair", "axpy|copy")[0] == 2  # no groups: every match keys as ()
+
+
+def test_a_paired_kernel_with_an_extra_instruction_is_different(tmp_path, capsys):
+    status, out = run(tmp_path, capsys, RENAMED_EXTRA, "--pair", "(axpy)")
+    assert status == 1
+    assert "1 identical, 0 operand-order, 1 different, 0 only in A, 0 only in B" in out and "v_mov_b32_e32 0 -> 1" in out
 
 
 def test_swap_with_other_registers_or_counts_is_different():
