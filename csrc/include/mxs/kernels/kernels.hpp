@@ -15,6 +15,8 @@
 //                                                kernels/stencil_levels.hip, stencil_pipe_levels[_src]_f32/_f64.hip
 //          mg_smooth, mg_residual_restrict, mg_prolong_add, mg_coarse_solve (the multigrid V-cycle)
 //                                                kernels/multigrid.hip
+//          cg_start, cg_apply, cg_update (conjugate gradients with fused dot products)
+//                                                kernels/cg.hip
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -24,6 +26,7 @@
 #include <limits>
 
 #include "mxs/grid/layout.hpp"
+#include "mxs/kernels/cg.hpp"
 #include "mxs/kernels/chunk_schedule.hpp"
 #include "mxs/kernels/fixed_edge_split.hpp"
 #include "mxs/kernels/multigrid.hpp"
@@ -359,6 +362,48 @@ void mg_coarse_solve(const T* src, T* e, const TileGeom& g, const MgSweepTable& 
 // names above; "" before the first): a host-side record like
 // last_stencil_dispatch(), not updated by graph replays.
 const char* last_multigrid_dispatch();
+
+// ------------------------------------------------- conjugate gradients (kernels/cg.hip)
+// The three kernels of one-process CG for L u = b, L v = (1 - c0) v - c1 (n + s
+// + w + e), on a core with a depth-1 Dirichlet ring (cg.hpp; docs/ARCHITECTURE.md
+// "Conjugate gradients"). Tiles share one geometry with a ring at least 1 deep;
+// any width, height >= 1. Each fuses its dot products: per-workgroup partials
+// and a last-block finish in a fixed order (the stencil5_residual recipe), all
+// sums and scalars in double, no floating-point atomics, no workgroup waits on
+// another. `partials` holds 2 * cg_grid_size(g) doubles; `counter` is one
+// unsigned that is 0 before the first launch (the last workgroup of every
+// launch puts the 0 back). With scalars->status != 0 at entry cg_apply and
+// cg_update store nothing at all. Each is bitwise equal to its reference in
+// ops/cg.py; the sums differ from it by their order only.
+//
+// cg_start ("cg_start"): r = (fma(c1, (n + s) + (w + e), c0 v) + g) - v over
+// the core, read from u with its ring and the core of g; p = r. Writes the
+// cores of r and p. Last workgroup: rr, linf, beta = 0, alpha = 0, pq = 0,
+// iteration = 0, status (1 if the chosen norm <= tol, else 2 if max_iters <= 0,
+// else 0). tol, max_iters and norm are the host's.
+int cg_grid_size(const TileGeom& g);
+template <typename T>
+void cg_start(const T* u, const T* g, T* r, T* p, const TileGeom& geom, Stencil5Coeffs c, CgScalars* scalars,
+              double* partials, unsigned* counter, hipStream_t s);
+// cg_apply ("cg_apply"): p_new = fma(T(beta), p_old, r); q = fma(-c1, (n + s) +
+// (w + e), T(1 - c0) p_new) with p_new = 0 outside the core. The neighbours'
+// p_new in a workgroup's one-cell apron are recomputed from r and p_old (same
+// formula, same bits). Reads the cores of r and p_old only, writes the cores of
+// p_new and q; p_old != p_new. Last workgroup: pq = sum p_new q, alpha = rr / pq
+// if pq > 0 and finite, otherwise alpha = 0 and status = 3.
+template <typename T>
+void cg_apply(const T* r, const T* p_old, T* p_new, T* q, const TileGeom& geom, Stencil5Coeffs c, CgScalars* scalars,
+              double* partials, unsigned* counter, hipStream_t s);
+// cg_update ("cg_update"): u = fma(T(alpha), p, u), r = fma(-T(alpha), q, r)
+// in place over the cores. Last workgroup: rr' = sum r^2, linf, beta = rr' / rr,
+// rr = rr', ++iteration, status (1 if the chosen norm <= tol, else 2 if
+// iteration == max_iters).
+template <typename T>
+void cg_update(T* u, T* r, const T* p, const T* q, const TileGeom& geom, CgScalars* scalars, double* partials,
+               unsigned* counter, hipStream_t s);
+// The kernel the most recent CG launcher of this host process ran ("" before
+// the first); not updated by graph replays.
+const char* last_cg_dispatch();
 
 // Whether work on stream b runs while a kernel on stream a still runs (the two
 // sit on different hardware queues): one bounded ~0.8 ms sleeping wave on a, a

@@ -10,6 +10,7 @@
 #include "mxs/grid/layout.hpp"
 #include "mxs/grid/regions.hpp"
 #include "mxs/halo/plan.hpp"
+#include "mxs/kernels/cg.hpp"
 #include "mxs/kernels/chunk_schedule.hpp"
 #include "mxs/kernels/fixed_edge_split.hpp"
 #include "mxs/kernels/multigrid.hpp"
@@ -326,6 +327,10 @@ PYBIND11_MODULE(_mxs_core, m) {
       py::arg("width"), py::arg("height"), py::arg("c_center"), py::arg("c_neighbor"), py::arg("coarse_reduction"),
       "the coarsest level's solve: the 32-level Leja-ordered Chebyshev cycle as a sweep table, its error bound rho "
       "and the smallest repeat count with rho^repeats <= coarse_reduction");
+  // Conjugate gradients (kernels/cg.hpp).
+  m.def("cg_check_operator", &kernels::cg_check_operator, py::arg("c_center"), py::arg("c_neighbor"),
+        "raises ValueError unless c_neighbor > 0 and c_center + 4 c_neighbor <= 1 + 1e-12 (then (1 - c_center) v - "
+        "c_neighbor (n + s + w + e) is symmetric positive definite)");
   m.attr("MG_COARSEN_ABOVE") = kernels::kMgCoarsenAbove;
   m.attr("MG_COARSEST_MAX") = kernels::kMgCoarsestMax;
   m.attr("MG_MAX_SMOOTH") = kernels::kMgMaxSmooth;

@@ -19,6 +19,7 @@
 #include "mxs/core/fault.hpp"
 #include "mxs/halo/exchange.hpp"
 #include "mxs/kernels/kernels.hpp"
+#include "mxs/runtime/cg_solver.hpp"
 #include "mxs/runtime/ipc.hpp"
 #include "mxs/runtime/multigrid_solver.hpp"
 #include "mxs/runtime/pingpong.hpp"
@@ -109,6 +110,31 @@ struct MultigridHandle {
     return dt == DType::F32 ? fn(*f) : fn(*d);
   }
 };
+
+struct CgHandle {
+  DType dt;
+  std::unique_ptr<CgSolver<float>> f;
+  std::unique_ptr<CgSolver<double>> d;
+  template <typename F>
+  auto visit(F&& fn) {
+    return dt == DType::F32 ? fn(*f) : fn(*d);
+  }
+};
+
+py::dict cg_scalars_dict(const kernels::CgScalars& s) {
+  py::dict d;
+  d["rr"] = s.rr;
+  d["pq"] = s.pq;
+  d["alpha"] = s.alpha;
+  d["beta"] = s.beta;
+  d["linf"] = s.linf;
+  d["tol"] = s.tol;
+  d["iteration"] = s.iteration;
+  d["max_iters"] = s.max_iters;
+  d["norm"] = s.norm;
+  d["status"] = s.status;
+  return d;
+}
 
 struct ExchangerHandle {
   DType dt;
@@ -1134,6 +1160,156 @@ PYBIND11_MODULE(_mxs_hip, m) {
       .def("graph_status", [](MultigridHandle& h) { return h.visit([](auto& s) { return s.graph_status(); }); })
       .def("launches_per_cycle", [](MultigridHandle& h) { return h.visit([](auto& s) { return s.launches_per_cycle(); }); })
       .def("note", [](MultigridHandle& h) { return h.visit([](auto& s) { return s.note(); }); });
+
+  // ------------------------------------------------------- conjugate gradients
+  // The launchers take the scalar block (CG_SCALARS_BYTES: doubles rr, pq, alpha,
+  // beta, linf, tol, then ints iteration, max_iters, norm, status), the partials
+  // (2 * cg_grid_size(geom) doubles) and the ticket (one unsigned, 0 before the
+  // first launch) as device addresses.
+  m.attr("CG_SCALARS_BYTES") = int(sizeof(kernels::CgScalars));
+  m.def("cg_grid_size", &kernels::cg_grid_size, py::arg("geom"), "workgroups of a CG launch at most (either type)");
+  m.def(
+      "cg_start",
+      [](std::uintptr_t u, std::uintptr_t g, std::uintptr_t r, std::uintptr_t p, const TileGeom& geom, double c0,
+         double c1, std::uintptr_t scalars, std::uintptr_t partials, std::uintptr_t counter, const std::string& dt,
+         std::uintptr_t s) {
+        kernels::Stencil5Coeffs c{c0, c1, false, -1.0};
+        if (parse_dtype(dt) == DType::F32)
+          kernels::cg_start<float>(ptr<float>(u), ptr<float>(g), ptr<float>(r), ptr<float>(p), geom, c,
+                                   ptr<kernels::CgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+        else
+          kernels::cg_start<double>(ptr<double>(u), ptr<double>(g), ptr<double>(r), ptr<double>(p), geom, c,
+                                    ptr<kernels::CgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+      },
+      py::arg("u"), py::arg("g"), py::arg("r"), py::arg("p"), py::arg("geom"), py::arg("c_center"), py::arg("c_neighbor"),
+      py::arg("scalars"), py::arg("partials"), py::arg("counter"), py::arg("dtype") = "f64", py::arg("stream") = 0,
+      "r = p = (fma(c1, (n + s) + (w + e), c0 v) + g) - v over the core; last workgroup: rr, linf, beta = 0, "
+      "iteration = 0, status");
+  m.def(
+      "cg_apply",
+      [](std::uintptr_t r, std::uintptr_t p_old, std::uintptr_t p_new, std::uintptr_t q, const TileGeom& geom, double c0,
+         double c1, std::uintptr_t scalars, std::uintptr_t partials, std::uintptr_t counter, const std::string& dt,
+         std::uintptr_t s) {
+        kernels::Stencil5Coeffs c{c0, c1, false, -1.0};
+        if (parse_dtype(dt) == DType::F32)
+          kernels::cg_apply<float>(ptr<float>(r), ptr<float>(p_old), ptr<float>(p_new), ptr<float>(q), geom, c,
+                                   ptr<kernels::CgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+        else
+          kernels::cg_apply<double>(ptr<double>(r), ptr<double>(p_old), ptr<double>(p_new), ptr<double>(q), geom, c,
+                                    ptr<kernels::CgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+      },
+      py::arg("r"), py::arg("p_old"), py::arg("p_new"), py::arg("q"), py::arg("geom"), py::arg("c_center"),
+      py::arg("c_neighbor"), py::arg("scalars"), py::arg("partials"), py::arg("counter"), py::arg("dtype") = "f64",
+      py::arg("stream") = 0,
+      "p_new = fma(T(beta), p_old, r), q = fma(-c1, (n + s) + (w + e), T(1 - c0) p_new) with p_new = 0 outside the "
+      "core; last workgroup: pq, alpha (or status 3)");
+  m.def(
+      "cg_update",
+      [](std::uintptr_t u, std::uintptr_t r, std::uintptr_t p, std::uintptr_t q, const TileGeom& geom,
+         std::uintptr_t scalars, std::uintptr_t partials, std::uintptr_t counter, const std::string& dt, std::uintptr_t s) {
+        if (parse_dtype(dt) == DType::F32)
+          kernels::cg_update<float>(ptr<float>(u), ptr<float>(r), ptr<float>(p), ptr<float>(q), geom,
+                                    ptr<kernels::CgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+        else
+          kernels::cg_update<double>(ptr<double>(u), ptr<double>(r), ptr<double>(p), ptr<double>(q), geom,
+                                     ptr<kernels::CgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+      },
+      py::arg("u"), py::arg("r"), py::arg("p"), py::arg("q"), py::arg("geom"), py::arg("scalars"), py::arg("partials"),
+      py::arg("counter"), py::arg("dtype") = "f64", py::arg("stream") = 0,
+      "u = fma(T(alpha), p, u), r = fma(-T(alpha), q, r) in place; last workgroup: rr, linf, beta, ++iteration, status");
+  m.def("last_cg_dispatch", [] { return std::string(kernels::last_cg_dispatch()); },
+        "the kernel the most recent CG launcher ran ('' before the first)");
+
+  py::class_<CgHandle>(m, "CgSolver")
+      .def(py::init([](index_t w, index_t h, const std::string& dt, double c0, double c1, bool graph) {
+             CgConfig cfg;
+             cfg.width = w;
+             cfg.height = h;
+             cfg.c_center = c0;
+             cfg.c_neighbor = c1;
+             cfg.graph = graph;
+             auto h_ = std::make_unique<CgHandle>();
+             h_->dt = parse_dtype(dt);
+             if (h_->dt == DType::F32) h_->f = std::make_unique<CgSolver<float>>(cfg);
+             else h_->d = std::make_unique<CgSolver<double>>(cfg);
+             return h_;
+           }),
+           py::arg("width"), py::arg("height"), py::arg("dtype") = "f64", py::arg("c_center") = 0.2,
+           py::arg("c_neighbor") = 0.2, py::arg("graph") = true)
+      .def("geom", [](CgHandle& h) { return h.visit([](auto& s) { return s.geom(); }); })
+      .def(
+          "set_boundary",
+          [](CgHandle& h, std::uintptr_t top, std::uintptr_t bottom, std::uintptr_t left, std::uintptr_t right) {
+            h.visit([&](auto& s) {
+              using T = typename std::decay_t<decltype(s)>::value_type;
+              s.set_boundary(ptr<T>(top), ptr<T>(bottom), ptr<T>(left), ptr<T>(right));
+            });
+          },
+          py::arg("top") = 0, py::arg("bottom") = 0, py::arg("left") = 0, py::arg("right") = 0,
+          "device pointers to width (top, bottom) / height (left, right) boundary values; 0 leaves a side as it is")
+      .def(
+          "set_source",
+          [](CgHandle& h, std::uintptr_t tile) {
+            h.visit([&](auto& s) {
+              using T = typename std::decay_t<decltype(s)>::value_type;
+              s.set_source(ptr<T>(tile));
+            });
+          },
+          py::arg("tile") = 0, "a device tile of geom() whose core holds g, or 0 (g = 0)")
+      .def("set_field",
+           [](CgHandle& h, std::uintptr_t tile) {
+             h.visit([&](auto& s) {
+               using T = typename std::decay_t<decltype(s)>::value_type;
+               s.set_field(ptr<T>(tile));
+             });
+           })
+      .def("field",
+           [](CgHandle& h, std::uintptr_t tile) {
+             h.visit([&](auto& s) {
+               using T = typename std::decay_t<decltype(s)>::value_type;
+               s.field(ptr<T>(tile));
+             });
+           })
+      .def("residual",
+           [](CgHandle& h) {
+             CgResidual r;
+             {
+               py::gil_scoped_release nogil;
+               r = h.visit([](auto& s) { return s.residual(); });
+             }
+             py::dict d;
+             d["linf"] = r.linf;
+             d["l2"] = r.l2;
+             d["cells"] = r.cells;
+             return d;
+           })
+      .def(
+          "solve",
+          [](CgHandle& h, double tol, int max_iters, const std::string& norm, int check_every) {
+            CgSolve r;
+            {
+              py::gil_scoped_release nogil;
+              r = h.visit([&](auto& s) { return s.solve(tol, max_iters, norm, check_every); });
+            }
+            py::dict d;
+            d["converged"] = r.converged;
+            d["iterations"] = r.iterations;
+            d["residual"] = r.residual;
+            d["reason"] = r.reason;
+            d["norm"] = r.norm;
+            d["restarts"] = r.restarts;
+            py::list hist;
+            for (const auto& c : r.history) hist.append(py::make_tuple(c.iteration, c.linf, c.l2));
+            d["history"] = hist;
+            return d;
+          },
+          py::arg("tol"), py::arg("max_iters") = 10000, py::arg("norm") = "l2", py::arg("check_every") = 32,
+          "cg_start, then blocks of check_every iterations and a read of the device scalars until the device stops; a "
+          "reported convergence is confirmed on the true residual (else a restart, 'stalled' after 3)")
+      .def("scalars", [](CgHandle& h) { return cg_scalars_dict(h.visit([](auto& s) { return s.scalars(); })); },
+           "the device scalar block as a dict (a synchronising read)")
+      .def("graph_status", [](CgHandle& h) { return h.visit([](auto& s) { return s.graph_status(); }); })
+      .def("note", [](CgHandle& h) { return h.visit([](auto& s) { return s.note(); }); });
 
   // ------------------------------------------------------------------ ping-pong
   py::enum_<PingPongMode>(m, "PingPongMode")

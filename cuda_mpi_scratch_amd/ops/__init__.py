@@ -1,5 +1,7 @@
 """Device ops: thin wrappers over the gfx950 HIP kernels (csrc/kernels), with
 exact CPU reference implementations for CPU tensors."""
+from .cg import (CgWorkspace, cg_apply, cg_apply_reference, cg_check_operator, cg_reference, cg_start,  # noqa: F401
+                 cg_start_reference, cg_update, cg_update_reference)
 from .dot import DotWorkspace, dot  # noqa: F401
 from .exact import box_exact_reference, stencil5_exact_periodic_reference, stencil5_exact_reference  # noqa: F401
 from .fill import fill, fill_random, fill_region, random_values  # noqa: F401
