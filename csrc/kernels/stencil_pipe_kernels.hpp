@@ -228,13 +228,19 @@ __device__ __forceinline__ void pipe_chunk(const typename B::T* __restrict__ in,
     const T* __restrict__ pin = in + core_off + lx;
     const index_t last_row = ye + S - 1;
     // The first PF rows (the D lead rows clamped to the first needed row when
-    // there is no wrap: they may lie above the ghost ring).
+    // there is no wrap: they may lie above the ghost ring; wrapped twice on a
+    // torus of fewer than S + D rows, H >= S > D, where one wrap leaves them
+    // above row 0).
     V pf[PF];
 #pragma unroll
     for (int k = 0; k < PF; ++k) {
       index_t r = ys - S - D + k;
-      if constexpr (WRAP) r = r < 0 ? r + H : r;
-      else r = r < ys - S ? ys - S : r;
+      if constexpr (WRAP) {
+        r = r < 0 ? r + H : r;
+        if constexpr (D > 0) r = r < 0 ? r + H : r;
+      } else {
+        r = r < ys - S ? ys - S : r;
+      }
       pf[k] = B::load(pin + r * pitch);
     }
     index_t first = ys - S - D + PF;

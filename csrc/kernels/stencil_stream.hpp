@@ -148,13 +148,24 @@ __device__ __forceinline__ void wave_prio_update(WavePrio& wp, index_t done) {
 // Buffer descriptor over a chunk's `rows` output rows from `obase` (wave-uniform,
 // and told so): the branch-free stores of stream_chunk_fast and pipe_chunk go
 // through it, and the hardware range check drops an offset past its range.
+// `obase` is the first column of the wave's 256-column window, so the range
+// ends with the window's last row: on a tile whose rows are shorter than the
+// window (pitch < 256; a wrapping pass needs no row padding) that is past
+// rows * pitch, and a range of rows * pitch dropped the last row's stores
+// beyond column pitch of the window. Never more than kMaxChunkBytes, which the
+// dropped offsets count on (only a piece of ~10^6 rows of such a tile gets there).
 template <typename T>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t chunk_out_rsrc(const T* obase, index_t rows, index_t pitch) {
   const unsigned long long ob = reinterpret_cast<unsigned long long>(obase);
   const unsigned ob_lo = __builtin_amdgcn_readfirstlane(unsigned(ob)),
                  ob_hi = __builtin_amdgcn_readfirstlane(unsigned(ob >> 32));
   T* obase_u = reinterpret_cast<T*>((static_cast<unsigned long long>(ob_hi) << 32) | ob_lo);
-  const int nbytes = __builtin_amdgcn_readfirstlane(int(rows * pitch * index_t(sizeof(T))));
+  constexpr index_t kWindow = 4 * kWaveSize;  // columns of a window: 4 cells per lane in both element types
+  index_t elems = rows * pitch;
+  if (pitch < kWindow && rows > 0) elems += kWindow - pitch;
+  index_t bytes = elems * index_t(sizeof(T));
+  bytes = bytes < kMaxChunkBytes ? bytes : kMaxChunkBytes;
+  const int nbytes = __builtin_amdgcn_readfirstlane(int(bytes));
   return __builtin_amdgcn_make_buffer_rsrc(obase_u, 0, nbytes, 0x00020000);
 }
 

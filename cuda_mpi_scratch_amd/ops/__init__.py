@@ -3,7 +3,8 @@ exact CPU reference implementations for CPU tensors."""
 from .cg import (CgWorkspace, cg_apply, cg_apply_reference, cg_check_operator, cg_reference, cg_start,  # noqa: F401
                  cg_start_reference, cg_update, cg_update_reference)
 from .dot import DotWorkspace, dot  # noqa: F401
-from .exact import box_exact_reference, stencil5_exact_periodic_reference, stencil5_exact_reference  # noqa: F401
+from .exact import (box_exact_reference, jacobi_sum_block_reference, stencil5_exact_block_reference,  # noqa: F401
+                    stencil5_exact_periodic_reference, stencil5_exact_reference)
 from .fill import fill, fill_random, fill_region, random_values  # noqa: F401
 from .multigrid import (mg_coarse_plan, mg_coarse_solve, mg_coarse_solve_reference, mg_plan_levels,  # noqa: F401
                         mg_prolong_add, mg_prolong_add_reference, mg_prolong_reference, mg_residual_reference,

@@ -14,6 +14,11 @@ arithmetic):
 * box: ``acc = 0``, then ``acc = fma(T(w_k), tap_k, acc)`` for ``ky`` outer,
   ``kx`` inner, the weights rounded to fp32 first.
 
+The time-blocked pass (``csrc/kernels/stencil.hip``: ``stencil5_tb``) is held to
+the same chain level by level: ``stencil5_exact_block_reference`` (per step, a
+ghost ring as deep as the block) and ``jacobi_sum_block_reference`` (the sum
+form's association on the same array).
+
 They work on plain 2-D arrays (core + ghost ring, or the periodic core), not on
 tiles.
 """
@@ -46,6 +51,42 @@ def stencil5_exact_periodic_reference(u: torch.Tensor, steps: int = 1, c_center:
         u = _jac(u, torch.roll(u, 1, 0), torch.roll(u, -1, 0), torch.roll(u, 1, 1), torch.roll(u, -1, 1), c_center,
                  c_neighbor)
     return u
+
+
+def stencil5_exact_block_reference(full: torch.Tensor, steps: int, c_center: float = 0.2,
+                                   c_neighbor: float = 0.2) -> torch.Tensor:
+    """The per-step time-blocked pass on a ghost-ring tile: ``steps``
+    applications of ``stencil5_exact_reference`` to a ``(h + 2 steps, w + 2 steps)``
+    array (core + a ghost ring ``steps`` deep). Every application drops the
+    outermost ring, so what is left is the ``(h, w)`` core after ``steps`` steps,
+    bitwise what ``stencil5_tb`` (``sum_form=False``, no wrap) must store."""
+    if full.shape[0] <= 2 * steps or full.shape[1] <= 2 * steps:
+        raise ValueError(f"stencil5_exact_block_reference: a {tuple(full.shape)} array has no core "
+                         f"under a ring of {steps}")
+    for _ in range(steps):
+        full = stencil5_exact_reference(full, c_center, c_neighbor)
+    return full
+
+
+def jacobi_sum_block_reference(full: torch.Tensor, steps: int, c: float = 0.2) -> torch.Tensor:
+    """The sum-form time-blocked pass on a ghost-ring tile: the ``(h, w)`` core of
+    ``jacobi_sum_reference_global`` applied to the ``(h + 2 steps, w + 2 steps)``
+    array as if it were a torus. A cell at least ``steps`` cells from the array's
+    edge never sees the wrap, so the core is what the pass computes from the
+    ring. The sum form pairs columns by the parity of the core column index
+    (the kernels' 4-cell vectors start at core columns that are multiples of 4):
+    with an odd ring the array gets one more column on the left, so that core
+    column 0 lands on an even column of the torus."""
+    if full.shape[0] <= 2 * steps or full.shape[1] <= 2 * steps:
+        raise ValueError(f"jacobi_sum_block_reference: a {tuple(full.shape)} array has no core "
+                         f"under a ring of {steps}")
+    from .stencil import jacobi_sum_reference_global
+
+    lead = steps % 2
+    if lead:
+        full = torch.nn.functional.pad(full, (1, 0))
+    out = jacobi_sum_reference_global(full, steps, c)
+    return out[steps:out.shape[0] - steps, steps + lead:out.shape[1] - steps].contiguous()
 
 
 def box_exact_reference(full: torch.Tensor, weights) -> torch.Tensor:

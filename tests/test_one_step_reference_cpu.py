@@ -90,6 +90,33 @@ def test_periodic_reference_equals_rational_arithmetic(dtype, c0, c1):
         assert _differing(ops.stencil5_exact_periodic_reference(u, steps, c0, c1), v, dtype) == 0
 
 
+def _bit_view(t: torch.Tensor) -> torch.Tensor:
+    return t.contiguous().view(torch.int32 if t.dtype == torch.float32 else torch.int64)
+
+
+@pytest.mark.parametrize("steps", [1, 2, 5, 9])
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+def test_block_reference_equals_the_level_reference_on_the_core(dtype, steps):
+    """S shrinking one-step applications against the level reference with no
+    side held (which keeps the array's size and lets its stale outermost ring
+    creep inwards): the same bits on the core, unequal coefficients."""
+    c0, c1 = 0.5, 0.125
+    full = _field((H + 2 * steps, W + 2 * steps), dtype, 20 + steps)
+    got = ops.stencil5_exact_block_reference(full, steps, c0, c1)
+    want = ops.jacobi_held_levels_reference(full, [c0] * steps, [c1] * steps, hold=0)[steps:-steps, steps:-steps]
+    assert got.shape == (H, W) and got.dtype == DT[dtype]
+    assert int((_bit_view(got) != _bit_view(want)).sum()) == 0
+    # ... and against the torus: far enough from the edge the ring is the wrap.
+    big = _field((H + 2 * steps + 3, W + 2 * steps + 2), dtype, 40 + steps)
+    per = ops.stencil5_exact_periodic_reference(big, steps, c0, c1)[steps:-steps, steps:-steps]
+    assert int((_bit_view(ops.stencil5_exact_block_reference(big, steps, c0, c1)) != _bit_view(per)).sum()) == 0
+
+
+def test_block_reference_needs_a_core():
+    with pytest.raises(ValueError):
+        ops.stencil5_exact_block_reference(_field((6, 9), "f32", 1), 3)
+
+
 def test_periodic_reference_folds_a_one_row_torus():
     """H = 1: rows -1 and H are the row itself."""
     u = _field((1, 4), "f64", 13)
