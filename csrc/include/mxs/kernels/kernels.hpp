@@ -16,6 +16,9 @@
 //          mg_smooth, mg_residual_restrict, mg_prolong_add, mg_coarse_solve (the multigrid V-cycle)
 //                                                kernels/multigrid.hip
 //          cg_start, cg_apply, cg_update (conjugate gradients with fused dot products)
+//          pcg_start, pcg_apply, pcg_update (the same bodies for preconditioned CG) kernels/cg.hip
+//          mgp_smooth, mgp_residual_restrict, mgp_prolong_add, mgp_coarse_solve (the any-size
+//          V-cycle preconditioner)            kernels/pcg_precond.hip
 //                                                kernels/cg.hip
 #pragma once
 
@@ -30,6 +33,7 @@
 #include "mxs/kernels/chunk_schedule.hpp"
 #include "mxs/kernels/fixed_edge_split.hpp"
 #include "mxs/kernels/multigrid.hpp"
+#include "mxs/kernels/pcg.hpp"
 #include "mxs/kernels/pipe_form.hpp"
 #include "mxs/kernels/relaxation.hpp"
 
@@ -404,6 +408,72 @@ void cg_update(T* u, T* r, const T* p, const T* q, const TileGeom& geom, CgScala
 // The kernel the most recent CG launcher of this host process ran ("" before
 // the first); not updated by graph replays.
 const char* last_cg_dispatch();
+
+// ---------------------------- preconditioned CG (kernels/cg.hip, kernels/pcg_precond.hip)
+// CG preconditioned by one any-size V-cycle (pcg.hpp; docs/ARCHITECTURE.md
+// "Preconditioned CG"). The pcg_* kernels are the cg_* bodies on a PcgScalars
+// block: the same expressions, grids, partials (2 * cg_grid_size(g) doubles) and
+// ticket; with scalars->status != 0 at entry pcg_apply and pcg_update store
+// nothing. Bitwise equal to ops/pcg.py, sums by their order only.
+//
+// pcg_start ("pcg_start"): cg_start's residual into the core of r (no first
+// direction). Last workgroup: rr, linf, rz = pq = alpha = beta = 0, iteration =
+// 0, status.
+template <typename T>
+void pcg_start(const T* u, const T* g, T* r, const TileGeom& geom, Stencil5Coeffs c, PcgScalars* scalars,
+               double* partials, unsigned* counter, hipStream_t s);
+// pcg_apply ("pcg_apply"): cg_apply with z = M r in place of r: p_new =
+// fma(T(beta), p_old, z) and the same q. Last workgroup: pq, alpha = rz / pq if
+// pq > 0 and finite, otherwise alpha = 0 and status = 3.
+template <typename T>
+void pcg_apply(const T* z, const T* p_old, T* p_new, T* q, const TileGeom& geom, Stencil5Coeffs c, PcgScalars* scalars,
+               double* partials, unsigned* counter, hipStream_t s);
+// pcg_update ("pcg_update"): cg_update's expressions. Last workgroup: rr, linf,
+// ++iteration, status; beta is not written (the dot epilogue owns it).
+template <typename T>
+void pcg_update(T* u, T* r, const T* p, const T* q, const TileGeom& geom, PcgScalars* scalars, double* partials,
+                unsigned* counter, hipStream_t s);
+
+// The preconditioner's kernels: the multigrid kernels for any size, with the
+// reflecting ghost of pcg.hpp. reflect_rows: the ghost row `height` reads as
+// minus core row height - 1 (the ring row there is never read); reflect_cols
+// likewise for column `width`. With both flags off and odd sides each gives the
+// bits of its mg_* namesake. Each is bitwise equal to its reference in
+// ops/pcg.py.
+//
+// mgp_smooth ("mgp_smooth"): mg_smooth with the flags: after every fused sweep
+// the staged ghost row / column of a reflecting side becomes the negated new
+// last core row / column (valid to the depth of the cell it mirrors). With
+// `scalars` (then partials and counter too: 2 * mgp_smooth_grid_size(g) doubles
+// and the CG ticket) the launch also sums src * u_out over the core in double,
+// fma(double(src), double(out), acc), and its last workgroup writes rz' = the
+// sum, beta = rz' / rz (0 while iteration == 0) and rz = rz' unless status != 0.
+// u_in == nullptr ("mgp_smooth_zero"): the iterate starts at 0 and no tile is
+// read for it; the bits are those of a launch on a zeroed u_in.
+int mgp_smooth_grid_size(const TileGeom& g);
+template <typename T>
+void mgp_smooth(const T* u_in, T* u_out, const T* src, const TileGeom& g, const MgSweepTable& t, bool reflect_rows,
+                bool reflect_cols, PcgScalars* scalars, double* partials, unsigned* counter, hipStream_t s);
+// mgp_residual_restrict ("mgp_residual_restrict"): mg_residual_restrict for a
+// coarse tile of (width / 2) x (height / 2): fine residuals outside the core
+// count as 0 (on an even side the last coarse cell's far neighbours), and the
+// residual reads the reflected ghost of a reflecting FINE level. The expression
+// and order of mg_residual_restrict.
+template <typename T>
+void mgp_residual_restrict(const T* u, const T* src, const TileGeom& g, bool reflect_rows, bool reflect_cols,
+                           T* coarse_src, const TileGeom& gc, Stencil5Coeffs c, hipStream_t s);
+// mgp_prolong_add ("mgp_prolong_add"): mg_prolong_add's kernel (e = 0 outside
+// the coarse core by index) for a coarse tile of (width / 2) x (height / 2).
+template <typename T>
+void mgp_prolong_add(const T* e, const TileGeom& gc, T* u, const TileGeom& g, hipStream_t s);
+// mgp_coarse_solve ("mgp_coarse_solve"): mg_coarse_solve with the flags: the
+// ghost row / column of a reflecting side is minus the last core row / column
+// at every sweep (minus zero at the start). With `scalars` (a single-level
+// preconditioner) it also sums src * e and writes rz and beta as mgp_smooth does.
+template <typename T>
+void mgp_coarse_solve(const T* src, T* e, const TileGeom& g, const MgSweepTable& t, int repeats, bool reflect_rows,
+                      bool reflect_cols, PcgScalars* scalars, hipStream_t s);
+const char* last_pcg_dispatch();
 
 // Whether work on stream b runs while a kernel on stream a still runs (the two
 // sit on different hardware queues): one bounded ~0.8 ms sleeping wave on a, a

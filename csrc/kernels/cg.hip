@@ -4,6 +4,10 @@
 // rides in the operator's pass and every dot product in the pass that makes
 // its terms, so an iteration streams 10 element arrays (apply: r, p_old in,
 // p_new, q out; update: u, r, p, q in, u, r out) and never a reduction pass.
+// The same three bodies, instantiated on PcgScalars, are pcg_start, pcg_apply
+// and pcg_update of multigrid-preconditioned CG (mxs/kernels/pcg.hpp): z = M r
+// stands for r in apply, alpha = rz / pq, and beta comes from the
+// preconditioner's dot epilogue (pcg_device.hpp) instead of update.
 //
 // Shape (that of residual.hip):
 //   * a lane owns one 16-byte vector (4 fp32 / 2 fp64 columns), a wave a strip
@@ -30,10 +34,12 @@
 #include <algorithm>
 #include <atomic>
 #include <cstdint>
+#include <type_traits>
 
 #include "mxs/core/error.hpp"
 #include "mxs/kernels/kernels.hpp"
 #include "mxs/runtime/hip_utils.hpp"
+#include "cg_reduce.hpp"
 
 // Every expression below is a rounding contract with ops/cg.py: the fused
 // multiply-adds that are meant are builtins, nothing else may be contracted.
@@ -43,8 +49,8 @@ namespace mxs {
 namespace kernels {
 namespace {
 
-constexpr int kCgWaves = 4;  // side by side along x
-constexpr int kCgBlock = kCgWaves * kWaveSize;
+using namespace cgdev;
+
 constexpr int kCh = 4;         // rows per chunk: row loads in flight per wave and array
 // Workgroups aimed at per CU. Every workgroup ends in an agent-scope release (a
 // write-back of its XCD's L2, which these kernels' own stores keep dirty), so
@@ -92,79 +98,6 @@ __device__ __forceinline__ double lane_shift(double v) {
   const int lo = __builtin_amdgcn_mov_dpp(int(b & 0xffffffff), CTRL, 0xf, 0xf, true);
   const int hi = __builtin_amdgcn_mov_dpp(int(b >> 32), CTRL, 0xf, 0xf, true);
   return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned int>(lo));
-}
-
-template <typename U>
-__device__ __forceinline__ U umax(U a, U b) {
-  return a > b ? a : b;
-}
-
-struct Pair {
-  double sum;
-  unsigned long long linf;  // bit pattern of a non-negative double (or a NaN)
-};
-
-// Workgroup reduction in a fixed order; valid in thread 0. lds: 2 * kCgWaves slots.
-__device__ __forceinline__ Pair block_reduce(Pair v, unsigned long long* lds) {
-#pragma unroll
-  for (int off = kWaveSize / 2; off > 0; off >>= 1) {
-    v.sum += __shfl_xor(v.sum, off);
-    v.linf = umax(v.linf, static_cast<unsigned long long>(__shfl_xor(static_cast<long long>(v.linf), off)));
-  }
-  const int lane = threadIdx.x & (kWaveSize - 1), wave = threadIdx.x / kWaveSize;
-  if (lane == 0) {
-    lds[2 * wave] = static_cast<unsigned long long>(__double_as_longlong(v.sum));
-    lds[2 * wave + 1] = v.linf;
-  }
-  __syncthreads();
-  Pair r{0.0, 0ull};
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int w = 0; w < kCgWaves; ++w) {
-      r.sum += __longlong_as_double(static_cast<long long>(lds[2 * w]));
-      r.linf = umax(r.linf, lds[2 * w + 1]);
-    }
-  }
-  return r;
-}
-
-// The launch's total, valid in thread 0 of the last workgroup to arrive (`last`
-// is workgroup-uniform). Every workgroup of the launch calls it exactly once.
-// The last workgroup puts the ticket back to 0 for the next launch.
-struct Total {
-  bool last;
-  double sum, linf;
-};
-__device__ __forceinline__ Total grid_reduce(double acc, unsigned long long linf_bits, double* partials,
-                                             unsigned* counter) {
-  // ONE __shared__ object (the "is last" flag shares the array, as in dot.hip).
-  __shared__ unsigned long long lds[4 * kCgWaves + 1];
-  const Pair r = block_reduce(Pair{acc, linf_bits}, lds);
-  volatile unsigned* flag = reinterpret_cast<volatile unsigned*>(lds + 4 * kCgWaves);
-  if (threadIdx.x == 0) {
-    partials[2 * index_t(blockIdx.x)] = r.sum;
-    partials[2 * index_t(blockIdx.x) + 1] = __longlong_as_double(static_cast<long long>(r.linf));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // the stores have left the wave
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // write back this XCD's L2 dirty lines
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *flag = (ticket == gridDim.x - 1) ? 1u : 0u;
-  }
-  __syncthreads();
-  if (*flag == 0u) return Total{false, 0.0, 0.0};  // workgroup-uniform
-  if (threadIdx.x == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // drop this CU's (possibly stale) L1 lines
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  __syncthreads();
-  Pair t{0.0, 0ull};
-  for (unsigned i = threadIdx.x; i < gridDim.x; i += kCgBlock) {  // fixed order per thread
-    t.sum += partials[2 * index_t(i)];
-    t.linf = umax(t.linf, static_cast<unsigned long long>(__double_as_longlong(partials[2 * index_t(i) + 1])));
-  }
-  const Pair total = block_reduce(t, lds + 2 * kCgWaves);
-  if (threadIdx.x == 0) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return Total{true, total.sum, __longlong_as_double(static_cast<long long>(total.linf))};
 }
 
 // The chosen norm of (rr, linf) against tol.
@@ -235,12 +168,14 @@ struct Edge {
 };
 
 // ------------------------------------------------------------------ cg_start
-template <typename T>
+// S: CgScalars (cg_*) or PcgScalars (pcg_*: no first direction is stored, rz = 0).
+template <typename T, typename S>
 __global__ __launch_bounds__(kCgBlock) void cg_start_kernel(const T* __restrict__ u, const T* __restrict__ g,
                                                             T* __restrict__ r, T* __restrict__ p, index_t pitch,
                                                             index_t core_off, index_t W, index_t H, unsigned gx,
-                                                            index_t band_rows, T c0, T c1, int vec_ok, CgScalars* sc,
+                                                            index_t band_rows, T c0, T c1, int vec_ok, S* sc,
                                                             double* partials, unsigned* counter) {
+  constexpr bool kPcg = std::is_same<S, PcgScalars>::value;
   constexpr int N = CgVec<T>::N;
   using V = typename CgVec<T>::type;
   using U = decltype(abs_bits(T(0)));
@@ -308,7 +243,7 @@ __global__ __launch_bounds__(kCgBlock) void cg_start_kernel(const T* __restrict_
             acc = __builtin_fma(double(res), double(res), acc);
           }
           L.st(rc, y + k, out);
-          L.st(pc, y + k, out);
+          if constexpr (!kPcg) L.st(pc, y + k, out);
         }
         up = mid;
         mid = dn[k];
@@ -323,6 +258,7 @@ __global__ __launch_bounds__(kCgBlock) void cg_start_kernel(const T* __restrict_
   const int max_iters = sc->max_iters;
   sc->rr = t.sum;
   sc->linf = t.linf;
+  if constexpr (kPcg) sc->rz = 0.0;
   sc->pq = 0.0;
   sc->alpha = 0.0;
   sc->beta = 0.0;
@@ -331,11 +267,12 @@ __global__ __launch_bounds__(kCgBlock) void cg_start_kernel(const T* __restrict_
 }
 
 // ------------------------------------------------------------------ cg_apply
-template <typename T>
+// S: CgScalars (alpha = rr / pq) or PcgScalars (r is z = M r, alpha = rz / pq).
+template <typename T, typename S>
 __global__ __launch_bounds__(kCgBlock) void cg_apply_kernel(const T* __restrict__ r, const T* __restrict__ po,
                                                             T* __restrict__ pn, T* __restrict__ q, index_t pitch,
                                                             index_t core_off, index_t W, index_t H, unsigned gx,
-                                                            index_t band_rows, T diag, T nc1, int vec_ok, CgScalars* sc,
+                                                            index_t band_rows, T diag, T nc1, int vec_ok, S* sc,
                                                             double* partials, unsigned* counter) {
   constexpr int N = CgVec<T>::N;
   using V = typename CgVec<T>::type;
@@ -435,7 +372,8 @@ __global__ __launch_bounds__(kCgBlock) void cg_apply_kernel(const T* __restrict_
   const double pq = t.sum;
   sc->pq = pq;
   if (pq > 0.0 && pq <= 1.7976931348623157e308) {
-    sc->alpha = sc->rr / pq;
+    if constexpr (std::is_same<S, PcgScalars>::value) sc->alpha = sc->rz / pq;
+    else sc->alpha = sc->rr / pq;
   } else {
     sc->alpha = 0.0;
     sc->status = kCgBreakdown;
@@ -443,11 +381,12 @@ __global__ __launch_bounds__(kCgBlock) void cg_apply_kernel(const T* __restrict_
 }
 
 // ----------------------------------------------------------------- cg_update
-template <typename T>
+// S: CgScalars (beta = rr' / rr) or PcgScalars (beta belongs to the preconditioner's dot epilogue).
+template <typename T, typename S>
 __global__ __launch_bounds__(kCgBlock) void cg_update_kernel(T* u, T* r, const T* __restrict__ p,
                                                              const T* __restrict__ q, index_t pitch, index_t core_off,
                                                              index_t W, index_t H, unsigned gx, index_t band_rows,
-                                                             int vec_ok, CgScalars* sc, double* partials,
+                                                             int vec_ok, S* sc, double* partials,
                                                              unsigned* counter) {
   constexpr int N = CgVec<T>::N;
   using V = typename CgVec<T>::type;
@@ -500,9 +439,8 @@ __global__ __launch_bounds__(kCgBlock) void cg_update_kernel(T* u, T* r, const T
 
   const Total t = grid_reduce(acc, static_cast<unsigned long long>(__double_as_longlong(from_bits(m))), partials, counter);
   if (!t.last || threadIdx.x != 0) return;
-  const double rr_old = sc->rr;
   const int it = sc->iteration + 1;
-  sc->beta = t.sum / rr_old;
+  if constexpr (std::is_same<S, CgScalars>::value) sc->beta = t.sum / sc->rr;
   sc->rr = t.sum;
   sc->linf = t.linf;
   sc->iteration = it;
@@ -536,7 +474,7 @@ bool aligned16(const T* tile, const TileGeom& g) {
 
 // The checks every launcher shares; returns the grid.
 template <typename T>
-CgGrid check(const char* who, const TileGeom& g, std::initializer_list<const T*> tiles, const CgScalars* scalars,
+CgGrid check(const char* who, const TileGeom& g, std::initializer_list<const T*> tiles, const void* scalars,
              const double* partials, const unsigned* counter) {
   MXS_CHECK(g.halo_x >= 1 && g.halo_y >= 1, who << ": the tile has no ghost ring (it needs one at least 1 deep)");
   MXS_CHECK(g.width >= 1 && g.height >= 1 && g.pitch >= g.x_origin + g.total_width(), who << ": bad tile geometry");
@@ -570,7 +508,7 @@ void cg_start(const T* u, const T* g, T* r, T* p, const TileGeom& geom, Stencil5
   constexpr int N = CgVec<T>::N;
   const int vec_ok = geom.pitch % N == 0 && aligned16(u, geom) && aligned16(g, geom) && aligned16(r, geom) &&
                      aligned16(p, geom);
-  cg_start_kernel<T><<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(
+  cg_start_kernel<T, CgScalars><<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(
       u, g, r, p, geom.pitch, geom.core_offset(), geom.width, geom.height, cg.gx, cg.band_rows, T(c.center),
       T(c.neighbor), vec_ok, scalars, partials, counter);
   g_last_cg = "cg_start";
@@ -587,7 +525,7 @@ void cg_apply(const T* r, const T* p_old, T* p_new, T* q, const TileGeom& geom, 
   constexpr int N = CgVec<T>::N;
   const int vec_ok = geom.pitch % N == 0 && aligned16(r, geom) && aligned16(p_old, geom) && aligned16(p_new, geom) &&
                      aligned16(q, geom);
-  cg_apply_kernel<T><<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(
+  cg_apply_kernel<T, CgScalars><<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(
       r, p_old, p_new, q, geom.pitch, geom.core_offset(), geom.width, geom.height, cg.gx, cg.band_rows,
       T(1.0 - c.center), T(-c.neighbor), vec_ok, scalars, partials, counter);
   g_last_cg = "cg_apply";
@@ -602,10 +540,57 @@ void cg_update(T* u, T* r, const T* p, const T* q, const TileGeom& geom, CgScala
   constexpr int N = CgVec<T>::N;
   const int vec_ok = geom.pitch % N == 0 && aligned16(u, geom) && aligned16(r, geom) && aligned16(p, geom) &&
                      aligned16(q, geom);
-  cg_update_kernel<T><<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(
+  cg_update_kernel<T, CgScalars><<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(
       u, r, p, q, geom.pitch, geom.core_offset(), geom.width, geom.height, cg.gx, cg.band_rows, vec_ok, scalars,
       partials, counter);
   g_last_cg = "cg_update";
+  MXS_HIP_CHECK_LAUNCH();
+}
+
+// -------------------------------------------------------- preconditioned CG
+template <typename T>
+void pcg_start(const T* u, const T* g, T* r, const TileGeom& geom, Stencil5Coeffs c, PcgScalars* scalars,
+               double* partials, unsigned* counter, hipStream_t s) {
+  const CgGrid cg = check<T>("pcg_start", geom, {u, g, r}, scalars, partials, counter);
+  MXS_CHECK(u != r && g != r && u != g, "pcg_start: u, g and r must be three tiles");
+  constexpr int N = CgVec<T>::N;
+  const int vec_ok = geom.pitch % N == 0 && aligned16(u, geom) && aligned16(g, geom) && aligned16(r, geom);
+  cg_start_kernel<T, PcgScalars><<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(
+      u, g, r, static_cast<T*>(nullptr), geom.pitch, geom.core_offset(), geom.width, geom.height, cg.gx, cg.band_rows,
+      T(c.center), T(c.neighbor), vec_ok, scalars, partials, counter);
+  g_last_cg = "pcg_start";
+  MXS_HIP_CHECK_LAUNCH();
+}
+
+template <typename T>
+void pcg_apply(const T* z, const T* p_old, T* p_new, T* q, const TileGeom& geom, Stencil5Coeffs c, PcgScalars* scalars,
+               double* partials, unsigned* counter, hipStream_t s) {
+  const CgGrid cg = check<T>("pcg_apply", geom, {z, p_old, p_new, q}, scalars, partials, counter);
+  MXS_CHECK(p_old != p_new, "pcg_apply: p_old != p_new (neighbouring workgroups still read p_old: pass the other "
+                            "buffer of the ping-pong pair)");
+  MXS_CHECK(z != p_new && z != q && p_old != q && p_new != q, "pcg_apply: z, p_old, p_new and q must be four tiles");
+  constexpr int N = CgVec<T>::N;
+  const int vec_ok = geom.pitch % N == 0 && aligned16(z, geom) && aligned16(p_old, geom) && aligned16(p_new, geom) &&
+                     aligned16(q, geom);
+  cg_apply_kernel<T, PcgScalars><<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(
+      z, p_old, p_new, q, geom.pitch, geom.core_offset(), geom.width, geom.height, cg.gx, cg.band_rows,
+      T(1.0 - c.center), T(-c.neighbor), vec_ok, scalars, partials, counter);
+  g_last_cg = "pcg_apply";
+  MXS_HIP_CHECK_LAUNCH();
+}
+
+template <typename T>
+void pcg_update(T* u, T* r, const T* p, const T* q, const TileGeom& geom, PcgScalars* scalars, double* partials,
+                unsigned* counter, hipStream_t s) {
+  const CgGrid cg = check<T>("pcg_update", geom, {u, r, p, q}, scalars, partials, counter);
+  MXS_CHECK(u != r && u != p && u != q && r != p && r != q && p != q, "pcg_update: u, r, p and q must be four tiles");
+  constexpr int N = CgVec<T>::N;
+  const int vec_ok = geom.pitch % N == 0 && aligned16(u, geom) && aligned16(r, geom) && aligned16(p, geom) &&
+                     aligned16(q, geom);
+  cg_update_kernel<T, PcgScalars><<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(
+      u, r, p, q, geom.pitch, geom.core_offset(), geom.width, geom.height, cg.gx, cg.band_rows, vec_ok, scalars,
+      partials, counter);
+  g_last_cg = "pcg_update";
   MXS_HIP_CHECK_LAUNCH();
 }
 
@@ -614,7 +599,12 @@ void cg_update(T* u, T* r, const T* p, const T* q, const TileGeom& geom, CgScala
                             unsigned*, hipStream_t);                                                                \
   template void cg_apply<T>(const T*, const T*, T*, T*, const TileGeom&, Stencil5Coeffs, CgScalars*, double*,       \
                             unsigned*, hipStream_t);                                                                \
-  template void cg_update<T>(T*, T*, const T*, const T*, const TileGeom&, CgScalars*, double*, unsigned*, hipStream_t);
+  template void cg_update<T>(T*, T*, const T*, const T*, const TileGeom&, CgScalars*, double*, unsigned*, hipStream_t); \
+  template void pcg_start<T>(const T*, const T*, T*, const TileGeom&, Stencil5Coeffs, PcgScalars*, double*, unsigned*, \
+                             hipStream_t);                                                                             \
+  template void pcg_apply<T>(const T*, const T*, T*, T*, const TileGeom&, Stencil5Coeffs, PcgScalars*, double*,       \
+                             unsigned*, hipStream_t);                                                                  \
+  template void pcg_update<T>(T*, T*, const T*, const T*, const TileGeom&, PcgScalars*, double*, unsigned*, hipStream_t);
 MXS_CG_INSTANTIATE(float)
 MXS_CG_INSTANTIATE(double)
 #undef MXS_CG_INSTANTIATE

@@ -14,6 +14,7 @@
 #include "mxs/kernels/chunk_schedule.hpp"
 #include "mxs/kernels/fixed_edge_split.hpp"
 #include "mxs/kernels/multigrid.hpp"
+#include "mxs/kernels/pcg.hpp"
 #include "mxs/kernels/relaxation.hpp"
 #include "mxs/runtime/call_plan.hpp"
 #include "mxs/runtime/decision.hpp"
@@ -331,6 +332,73 @@ PYBIND11_MODULE(_mxs_core, m) {
   m.def("cg_check_operator", &kernels::cg_check_operator, py::arg("c_center"), py::arg("c_neighbor"),
         "raises ValueError unless c_neighbor > 0 and c_center + 4 c_neighbor <= 1 + 1e-12 (then (1 - c_center) v - "
         "c_neighbor (n + s + w + e) is symmetric positive definite)");
+  // Preconditioned CG (kernels/pcg.hpp): the any-size level plan and the coarse solve plan.
+  auto pcg_level_dict = [](const kernels::PcgLevel& l) {
+    py::dict d;
+    d["width"] = l.width;
+    d["height"] = l.height;
+    d["reflect_rows"] = l.reflect_rows;
+    d["reflect_cols"] = l.reflect_cols;
+    d["c_center"] = l.c0;
+    return d;
+  };
+  m.def(
+      "pcg_plan_levels",
+      [pcg_level_dict](long long w, long long h, double c0, double c1) {
+        py::list out;
+        for (const kernels::PcgLevel& l : kernels::pcg_plan_levels(w, h, c0, c1)) out.append(pcg_level_dict(l));
+        return out;
+      },
+      py::arg("width"), py::arg("height"), py::arg("c_center") = 0.2, py::arg("c_neighbor") = 0.2,
+      "the preconditioner's levels of a width x height core, finest first, as dicts (width, height, reflect_rows, "
+      "reflect_cols, c_center): n_c = floor(n / 2) on both axes while the larger side is above 31 and the smaller at "
+      "least 2; a flag is set when the parent's height (rows) or width (cols) was even; raises ValueError when the "
+      "coarsest level is above 63 on a side (the message names ConjugateGradient2D)");
+  auto pcg_level_of = [](long long w, long long h, bool rr, bool rc, double c0) {
+    kernels::PcgLevel l;
+    l.width = w;
+    l.height = h;
+    l.reflect_rows = rr;
+    l.reflect_cols = rc;
+    l.c0 = c0;
+    return l;
+  };
+  m.def(
+      "pcg_coarse_interval",
+      [pcg_level_of](long long w, long long h, bool rr, bool rc, double c0, double c1) {
+        const kernels::RelaxSpectrum sp = kernels::pcg_coarse_interval(pcg_level_of(w, h, rr, rc, c0), c1);
+        return std::make_pair(sp.a, sp.b);
+      },
+      py::arg("width"), py::arg("height"), py::arg("reflect_rows"), py::arg("reflect_cols"), py::arg("c_center"),
+      py::arg("c_neighbor"),
+      "(a, b) the coarse solve of a level is built on: relaxation_spectrum's, with the Gershgorin upper end "
+      "1 - c_center + 4 c_neighbor when a side reflects");
+  m.def(
+      "pcg_coarse_plan",
+      [sweep_dict, pcg_level_of](long long w, long long h, bool rr, bool rc, double c0, double c1, double reduction) {
+        const kernels::MgCoarsePlan p = kernels::pcg_coarse_plan(pcg_level_of(w, h, rr, rc, c0), c1, reduction);
+        py::dict d = sweep_dict(p.table);
+        d["repeats"] = p.repeats;
+        d["rho"] = p.rho;
+        return d;
+      },
+      py::arg("width"), py::arg("height"), py::arg("reflect_rows"), py::arg("reflect_cols"), py::arg("c_center"),
+      py::arg("c_neighbor"), py::arg("coarse_reduction"),
+      "the coarsest level's solve: mg_coarse_plan without a reflecting side, else the 32-level cycle of pcg_coarse_interval");
+  m.def(
+      "chebyshev_cycle_interval",
+      [](double a, double b, double c0, double c1, int M) {
+        const kernels::LevelTable t = kernels::chebyshev_cycle_interval(a, b, c0, c1, M);
+        py::dict d;
+        d["n"] = t.n;
+        d["center"] = std::vector<double>(t.center, t.center + t.n);
+        d["neighbor"] = std::vector<double>(t.neighbor, t.neighbor + t.n);
+        d["growth"] = t.growth;
+        return d;
+      },
+      py::arg("a"), py::arg("b"), py::arg("c_center"), py::arg("c_neighbor"), py::arg("levels"),
+      "chebyshev_cycle on a given interval 0 < a < b of I - A: the same roots, Leja order and tables");
+  m.attr("PCG_SCALARS_BYTES") = int(sizeof(kernels::PcgScalars));
   m.attr("MG_COARSEN_ABOVE") = kernels::kMgCoarsenAbove;
   m.attr("MG_COARSEST_MAX") = kernels::kMgCoarsestMax;
   m.attr("MG_MAX_SMOOTH") = kernels::kMgMaxSmooth;

@@ -22,6 +22,7 @@
 #include "mxs/runtime/cg_solver.hpp"
 #include "mxs/runtime/ipc.hpp"
 #include "mxs/runtime/multigrid_solver.hpp"
+#include "mxs/runtime/pcg_solver.hpp"
 #include "mxs/runtime/pingpong.hpp"
 #include "mxs/runtime/stencil_solver.hpp"
 
@@ -120,6 +121,32 @@ struct CgHandle {
     return dt == DType::F32 ? fn(*f) : fn(*d);
   }
 };
+
+struct PcgHandle {
+  DType dt;
+  std::unique_ptr<PcgSolver<float>> f;
+  std::unique_ptr<PcgSolver<double>> d;
+  template <typename F>
+  auto visit(F&& fn) {
+    return dt == DType::F32 ? fn(*f) : fn(*d);
+  }
+};
+
+py::dict pcg_scalars_dict(const kernels::PcgScalars& s) {
+  py::dict d;
+  d["rr"] = s.rr;
+  d["rz"] = s.rz;
+  d["pq"] = s.pq;
+  d["alpha"] = s.alpha;
+  d["beta"] = s.beta;
+  d["linf"] = s.linf;
+  d["tol"] = s.tol;
+  d["iteration"] = s.iteration;
+  d["max_iters"] = s.max_iters;
+  d["norm"] = s.norm;
+  d["status"] = s.status;
+  return d;
+}
 
 py::dict cg_scalars_dict(const kernels::CgScalars& s) {
   py::dict d;
@@ -1310,6 +1337,227 @@ PYBIND11_MODULE(_mxs_hip, m) {
            "the device scalar block as a dict (a synchronising read)")
       .def("graph_status", [](CgHandle& h) { return h.visit([](auto& s) { return s.graph_status(); }); })
       .def("note", [](CgHandle& h) { return h.visit([](auto& s) { return s.note(); }); });
+
+  // ---------------------------------------------------------- preconditioned CG
+  // The scalar block is PCG_SCALARS_BYTES: doubles rr, rz, pq, alpha, beta, linf,
+  // tol, then ints iteration, max_iters, norm, status. Partials: 2 *
+  // cg_grid_size(geom) doubles for pcg_*, 2 * mgp_smooth_grid_size(geom) for the
+  // smoother's dot epilogue; the ticket is CG's.
+  m.attr("PCG_SCALARS_BYTES") = int(sizeof(kernels::PcgScalars));
+  m.def("mgp_smooth_grid_size", &kernels::mgp_smooth_grid_size, py::arg("geom"), "workgroups of an mgp_smooth launch");
+  m.def(
+      "pcg_start",
+      [](std::uintptr_t u, std::uintptr_t g, std::uintptr_t r, const TileGeom& geom, double c0, double c1,
+         std::uintptr_t scalars, std::uintptr_t partials, std::uintptr_t counter, const std::string& dt, std::uintptr_t s) {
+        kernels::Stencil5Coeffs c{c0, c1, false, -1.0};
+        if (parse_dtype(dt) == DType::F32)
+          kernels::pcg_start<float>(ptr<float>(u), ptr<float>(g), ptr<float>(r), geom, c,
+                                    ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+        else
+          kernels::pcg_start<double>(ptr<double>(u), ptr<double>(g), ptr<double>(r), geom, c,
+                                     ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+      },
+      py::arg("u"), py::arg("g"), py::arg("r"), py::arg("geom"), py::arg("c_center"), py::arg("c_neighbor"),
+      py::arg("scalars"), py::arg("partials"), py::arg("counter"), py::arg("dtype") = "f64", py::arg("stream") = 0,
+      "r = (fma(c1, (n + s) + (w + e), c0 v) + g) - v over the core; last workgroup: rr, linf, rz = beta = 0, "
+      "iteration = 0, status");
+  m.def(
+      "pcg_apply",
+      [](std::uintptr_t z, std::uintptr_t p_old, std::uintptr_t p_new, std::uintptr_t q, const TileGeom& geom, double c0,
+         double c1, std::uintptr_t scalars, std::uintptr_t partials, std::uintptr_t counter, const std::string& dt,
+         std::uintptr_t s) {
+        kernels::Stencil5Coeffs c{c0, c1, false, -1.0};
+        if (parse_dtype(dt) == DType::F32)
+          kernels::pcg_apply<float>(ptr<float>(z), ptr<float>(p_old), ptr<float>(p_new), ptr<float>(q), geom, c,
+                                    ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+        else
+          kernels::pcg_apply<double>(ptr<double>(z), ptr<double>(p_old), ptr<double>(p_new), ptr<double>(q), geom, c,
+                                     ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+      },
+      py::arg("z"), py::arg("p_old"), py::arg("p_new"), py::arg("q"), py::arg("geom"), py::arg("c_center"),
+      py::arg("c_neighbor"), py::arg("scalars"), py::arg("partials"), py::arg("counter"), py::arg("dtype") = "f64",
+      py::arg("stream") = 0,
+      "p_new = fma(T(beta), p_old, z), q = L p_new; last workgroup: pq, alpha = rz / pq (or status 3)");
+  m.def(
+      "pcg_update",
+      [](std::uintptr_t u, std::uintptr_t r, std::uintptr_t p, std::uintptr_t q, const TileGeom& geom,
+         std::uintptr_t scalars, std::uintptr_t partials, std::uintptr_t counter, const std::string& dt, std::uintptr_t s) {
+        if (parse_dtype(dt) == DType::F32)
+          kernels::pcg_update<float>(ptr<float>(u), ptr<float>(r), ptr<float>(p), ptr<float>(q), geom,
+                                     ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+        else
+          kernels::pcg_update<double>(ptr<double>(u), ptr<double>(r), ptr<double>(p), ptr<double>(q), geom,
+                                      ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+      },
+      py::arg("u"), py::arg("r"), py::arg("p"), py::arg("q"), py::arg("geom"), py::arg("scalars"), py::arg("partials"),
+      py::arg("counter"), py::arg("dtype") = "f64", py::arg("stream") = 0,
+      "u = fma(T(alpha), p, u), r = fma(-T(alpha), q, r) in place; last workgroup: rr, linf, ++iteration, status");
+  m.def(
+      "mgp_smooth",
+      [sweep_table](std::uintptr_t in, std::uintptr_t out, std::uintptr_t src, const TileGeom& g,
+                    const std::vector<double>& center, const std::vector<double>& neighbor,
+                    const std::vector<double>& weight, bool rr, bool rc, std::uintptr_t scalars, std::uintptr_t partials,
+                    std::uintptr_t counter, const std::string& dt, std::uintptr_t s) {
+        const kernels::MgSweepTable t = sweep_table(center, neighbor, weight);
+        if (parse_dtype(dt) == DType::F32)
+          kernels::mgp_smooth<float>(ptr<float>(in), ptr<float>(out), ptr<float>(src), g, t, rr, rc,
+                                     ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+        else
+          kernels::mgp_smooth<double>(ptr<double>(in), ptr<double>(out), ptr<double>(src), g, t, rr, rc,
+                                      ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+      },
+      py::arg("u_in"), py::arg("u_out"), py::arg("src"), py::arg("geom"), py::arg("center"), py::arg("neighbor"),
+      py::arg("weight"), py::arg("reflect_rows") = false, py::arg("reflect_cols") = false, py::arg("scalars") = 0,
+      py::arg("partials") = 0, py::arg("counter") = 0, py::arg("dtype") = "f32", py::arg("stream") = 0,
+      "mg_smooth with reflecting ghosts; with scalars, partials and counter also the dot epilogue (rz, beta)");
+  m.def(
+      "mgp_residual_restrict",
+      [](std::uintptr_t u, std::uintptr_t src, const TileGeom& g, bool rr, bool rc, std::uintptr_t csrc, const TileGeom& gc,
+         double c0, double c1, const std::string& dt, std::uintptr_t s) {
+        kernels::Stencil5Coeffs c{c0, c1, false, -1.0};
+        if (parse_dtype(dt) == DType::F32)
+          kernels::mgp_residual_restrict<float>(ptr<float>(u), ptr<float>(src), g, rr, rc, ptr<float>(csrc), gc, c, strm(s));
+        else
+          kernels::mgp_residual_restrict<double>(ptr<double>(u), ptr<double>(src), g, rr, rc, ptr<double>(csrc), gc, c,
+                                                 strm(s));
+      },
+      py::arg("u"), py::arg("src"), py::arg("geom"), py::arg("reflect_rows"), py::arg("reflect_cols"),
+      py::arg("coarse_src"), py::arg("coarse_geom"), py::arg("c_center") = 0.2, py::arg("c_neighbor") = 0.2,
+      py::arg("dtype") = "f32", py::arg("stream") = 0,
+      "coarse_src core = 4 R ((A u + src) - u) for a coarse tile of (width / 2) x (height / 2), fine residuals outside "
+      "the core 0, the fine level's reflecting ghost read");
+  m.def(
+      "mgp_prolong_add",
+      [](std::uintptr_t e, const TileGeom& gc, std::uintptr_t u, const TileGeom& g, const std::string& dt,
+         std::uintptr_t s) {
+        if (parse_dtype(dt) == DType::F32) kernels::mgp_prolong_add<float>(ptr<float>(e), gc, ptr<float>(u), g, strm(s));
+        else kernels::mgp_prolong_add<double>(ptr<double>(e), gc, ptr<double>(u), g, strm(s));
+      },
+      py::arg("e"), py::arg("coarse_geom"), py::arg("u"), py::arg("geom"), py::arg("dtype") = "f32",
+      py::arg("stream") = 0, "u core += P e for a coarse tile of (width / 2) x (height / 2)");
+  m.def(
+      "mgp_coarse_solve",
+      [sweep_table](std::uintptr_t src, std::uintptr_t e, const TileGeom& g, const std::vector<double>& center,
+                    const std::vector<double>& neighbor, const std::vector<double>& weight, int repeats, bool rr, bool rc,
+                    std::uintptr_t scalars, const std::string& dt, std::uintptr_t s) {
+        const kernels::MgSweepTable t = sweep_table(center, neighbor, weight);
+        if (parse_dtype(dt) == DType::F32)
+          kernels::mgp_coarse_solve<float>(ptr<float>(src), ptr<float>(e), g, t, repeats, rr, rc,
+                                           ptr<kernels::PcgScalars>(scalars), strm(s));
+        else
+          kernels::mgp_coarse_solve<double>(ptr<double>(src), ptr<double>(e), g, t, repeats, rr, rc,
+                                            ptr<kernels::PcgScalars>(scalars), strm(s));
+      },
+      py::arg("src"), py::arg("e"), py::arg("geom"), py::arg("center"), py::arg("neighbor"), py::arg("weight"),
+      py::arg("repeats"), py::arg("reflect_rows") = false, py::arg("reflect_cols") = false, py::arg("scalars") = 0,
+      py::arg("dtype") = "f32", py::arg("stream") = 0,
+      "mg_coarse_solve with reflecting ghosts; with scalars also the dot epilogue of a single-level preconditioner");
+  m.def("last_pcg_dispatch", [] { return std::string(kernels::last_pcg_dispatch()); },
+        "the kernel the most recent preconditioner launcher ran ('' before the first)");
+
+  py::class_<PcgHandle>(m, "PcgSolver")
+      .def(py::init([](index_t w, index_t h, const std::string& dt, double c0, double c1, int nu, double omega,
+                       double coarse_reduction, bool graph) {
+             PcgConfig cfg;
+             cfg.width = w;
+             cfg.height = h;
+             cfg.c_center = c0;
+             cfg.c_neighbor = c1;
+             cfg.nu = nu;
+             cfg.smoother_omega = omega;
+             cfg.coarse_reduction = coarse_reduction;
+             cfg.graph = graph;
+             auto h_ = std::make_unique<PcgHandle>();
+             h_->dt = parse_dtype(dt);
+             if (h_->dt == DType::F32) h_->f = std::make_unique<PcgSolver<float>>(cfg);
+             else h_->d = std::make_unique<PcgSolver<double>>(cfg);
+             return h_;
+           }),
+           py::arg("width"), py::arg("height"), py::arg("dtype") = "f64", py::arg("c_center") = 0.2,
+           py::arg("c_neighbor") = 0.2, py::arg("nu") = 2, py::arg("smoother_omega") = 0.8,
+           py::arg("coarse_reduction") = 1e-3, py::arg("graph") = true)
+      .def("geom", [](PcgHandle& h) { return h.visit([](auto& s) { return s.geom(); }); })
+      .def("levels",
+           [](PcgHandle& h) {
+             py::list out;
+             h.visit([&](auto& s) {
+               for (const auto& l : s.levels())
+                 out.append(py::make_tuple(l.width, l.height, l.reflect_rows, l.reflect_cols, l.c0));
+             });
+             return out;
+           })
+      .def(
+          "set_boundary",
+          [](PcgHandle& h, std::uintptr_t top, std::uintptr_t bottom, std::uintptr_t left, std::uintptr_t right) {
+            h.visit([&](auto& s) {
+              using T = typename std::decay_t<decltype(s)>::value_type;
+              s.set_boundary(ptr<T>(top), ptr<T>(bottom), ptr<T>(left), ptr<T>(right));
+            });
+          },
+          py::arg("top") = 0, py::arg("bottom") = 0, py::arg("left") = 0, py::arg("right") = 0)
+      .def(
+          "set_source",
+          [](PcgHandle& h, std::uintptr_t tile) {
+            h.visit([&](auto& s) {
+              using T = typename std::decay_t<decltype(s)>::value_type;
+              s.set_source(ptr<T>(tile));
+            });
+          },
+          py::arg("tile") = 0)
+      .def("set_field",
+           [](PcgHandle& h, std::uintptr_t tile) {
+             h.visit([&](auto& s) {
+               using T = typename std::decay_t<decltype(s)>::value_type;
+               s.set_field(ptr<T>(tile));
+             });
+           })
+      .def("field",
+           [](PcgHandle& h, std::uintptr_t tile) {
+             h.visit([&](auto& s) {
+               using T = typename std::decay_t<decltype(s)>::value_type;
+               s.field(ptr<T>(tile));
+             });
+           })
+      .def("residual",
+           [](PcgHandle& h) {
+             CgResidual r;
+             {
+               py::gil_scoped_release nogil;
+               r = h.visit([](auto& s) { return s.residual(); });
+             }
+             py::dict d;
+             d["linf"] = r.linf;
+             d["l2"] = r.l2;
+             d["cells"] = r.cells;
+             return d;
+           })
+      .def(
+          "solve",
+          [](PcgHandle& h, double tol, int max_iters, const std::string& norm, int check_every) {
+            CgSolve r;
+            {
+              py::gil_scoped_release nogil;
+              r = h.visit([&](auto& s) { return s.solve(tol, max_iters, norm, check_every); });
+            }
+            py::dict d;
+            d["converged"] = r.converged;
+            d["iterations"] = r.iterations;
+            d["residual"] = r.residual;
+            d["reason"] = r.reason;
+            d["norm"] = r.norm;
+            d["restarts"] = r.restarts;
+            py::list hist;
+            for (const auto& c : r.history) hist.append(py::make_tuple(c.iteration, c.linf, c.l2));
+            d["history"] = hist;
+            return d;
+          },
+          py::arg("tol"), py::arg("max_iters") = 1000, py::arg("norm") = "l2", py::arg("check_every") = 2,
+          "pcg_start, then blocks of check_every iterations (V-cycle, pcg_apply, pcg_update) and a read of the device "
+          "scalars until the device stops; a reported convergence is confirmed on the true residual")
+      .def("scalars", [](PcgHandle& h) { return pcg_scalars_dict(h.visit([](auto& s) { return s.scalars(); })); })
+      .def("graph_status", [](PcgHandle& h) { return h.visit([](auto& s) { return s.graph_status(); }); })
+      .def("launches_per_iteration", [](PcgHandle& h) { return h.visit([](auto& s) { return s.launches_per_iteration(); }); })
+      .def("note", [](PcgHandle& h) { return h.visit([](auto& s) { return s.note(); }); });
 
   // ------------------------------------------------------------------ ping-pong
   py::enum_<PingPongMode>(m, "PingPongMode")

@@ -10,6 +10,11 @@ from .multigrid import (mg_coarse_plan, mg_coarse_solve, mg_coarse_solve_referen
                         mg_prolong_add, mg_prolong_add_reference, mg_prolong_reference, mg_residual_reference,
                         mg_residual_restrict, mg_residual_restrict_reference, mg_restrict_reference, mg_smooth,
                         mg_smooth_reference, mg_smoother_table, multigrid_vcycle_reference)
+from .pcg import (PcgPlan, PcgWorkspace, chebyshev_cycle_interval, mgp_coarse_solve,  # noqa: F401
+                  mgp_coarse_solve_reference, mgp_prolong_add, mgp_prolong_add_reference, mgp_residual_restrict,
+                  mgp_residual_restrict_reference, mgp_smooth, mgp_smooth_reference, pcg_apply, pcg_coarse_interval,
+                  pcg_coarse_plan, pcg_plan_levels, pcg_plan_levels_twin, pcg_precondition_reference, pcg_reference,
+                  pcg_start, pcg_update)
 from .relaxation import (chebyshev_cycle, fma, jacobi_held_levels_reference, relaxation_spectrum,  # noqa: F401
                          stencil5_tb_held_levels, stencil5_tb_levels)
 from .source import jacobi_source_per_step_reference, source_correction_reference  # noqa: F401
