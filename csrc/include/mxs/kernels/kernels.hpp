@@ -388,7 +388,7 @@ const char* last_multigrid_dispatch();
 int cg_grid_size(const TileGeom& g);
 template <typename T>
 void cg_start(const T* u, const T* g, T* r, T* p, const TileGeom& geom, Stencil5Coeffs c, CgScalars* scalars,
-              double* partials, unsigned* counter, hipStream_t s);
+              double* partials, unsigned* counter, hipStream_t s, GhostSides sides = {});
 // cg_apply ("cg_apply"): p_new = fma(T(beta), p_old, r); q = fma(-c1, (n + s) +
 // (w + e), T(1 - c0) p_new) with p_new = 0 outside the core. The neighbours'
 // p_new in a workgroup's one-cell apron are recomputed from r and p_old (same
@@ -397,7 +397,13 @@ void cg_start(const T* u, const T* g, T* r, T* p, const TileGeom& geom, Stencil5
 // if pq > 0 and finite, otherwise alpha = 0 and status = 3.
 template <typename T>
 void cg_apply(const T* r, const T* p_old, T* p_new, T* q, const TileGeom& geom, Stencil5Coeffs c, CgScalars* scalars,
-              double* partials, unsigned* counter, hipStream_t s);
+              double* partials, unsigned* counter, hipStream_t s, GhostSides sides = {});
+// Sides (`sides`, cg.hpp's GhostSides: ring or mirror, all ring by default):
+// on a mirror side cg_start reads the ghost as edge + ring (one T addition, the
+// ring cell holding the prescribed difference d) and cg_apply as the edge cell
+// of p_new itself; only the global edges of the core mirror. With no mirror
+// side the launchers run the ring-only kernels, bit for bit as before.
+//
 // cg_update ("cg_update"): u = fma(T(alpha), p, u), r = fma(-T(alpha), q, r)
 // in place over the cores. Last workgroup: rr' = sum r^2, linf, beta = rr' / rr,
 // rr = rr', ++iteration, status (1 if the chosen norm <= tol, else 2 if
@@ -421,13 +427,13 @@ const char* last_cg_dispatch();
 // 0, status.
 template <typename T>
 void pcg_start(const T* u, const T* g, T* r, const TileGeom& geom, Stencil5Coeffs c, PcgScalars* scalars,
-               double* partials, unsigned* counter, hipStream_t s);
+               double* partials, unsigned* counter, hipStream_t s, GhostSides sides = {});
 // pcg_apply ("pcg_apply"): cg_apply with z = M r in place of r: p_new =
 // fma(T(beta), p_old, z) and the same q. Last workgroup: pq, alpha = rz / pq if
 // pq > 0 and finite, otherwise alpha = 0 and status = 3.
 template <typename T>
 void pcg_apply(const T* z, const T* p_old, T* p_new, T* q, const TileGeom& geom, Stencil5Coeffs c, PcgScalars* scalars,
-               double* partials, unsigned* counter, hipStream_t s);
+               double* partials, unsigned* counter, hipStream_t s, GhostSides sides = {});
 // pcg_update ("pcg_update"): cg_update's expressions. Last workgroup: rr, linf,
 // ++iteration, status; beta is not written (the dot epilogue owns it).
 template <typename T>
@@ -441,6 +447,15 @@ void pcg_update(T* u, T* r, const T* p, const T* q, const TileGeom& geom, PcgSca
 // bits of its mg_* namesake. Each is bitwise equal to its reference in
 // ops/pcg.py.
 //
+// Sides (`sides`, cg.hpp's GhostSides): a level's four ghost codes. Reflect
+// (-1, far sides only) is the flag of before: the ghost is minus the edge cell.
+// Mirror (+1, any side) is plus the edge cell, kept by the same mechanism: the
+// thread that advances an edge cell writes the ghost beside it. In the
+// transfers a mirror side also clamps the prolongation's coarse index (the
+// coarse ghost equals the mirrored coarse cell) and doubles the fine residual
+// of the row / column whose outer coarse neighbour is that ghost, so that
+// 4 R = P^T still holds (docs/ARCHITECTURE.md "Neumann sides").
+//
 // mgp_smooth ("mgp_smooth"): mg_smooth with the flags: after every fused sweep
 // the staged ghost row / column of a reflecting side becomes the negated new
 // last core row / column (valid to the depth of the cell it mirrors). With
@@ -452,27 +467,27 @@ void pcg_update(T* u, T* r, const T* p, const T* q, const TileGeom& geom, PcgSca
 // read for it; the bits are those of a launch on a zeroed u_in.
 int mgp_smooth_grid_size(const TileGeom& g);
 template <typename T>
-void mgp_smooth(const T* u_in, T* u_out, const T* src, const TileGeom& g, const MgSweepTable& t, bool reflect_rows,
-                bool reflect_cols, PcgScalars* scalars, double* partials, unsigned* counter, hipStream_t s);
+void mgp_smooth(const T* u_in, T* u_out, const T* src, const TileGeom& g, const MgSweepTable& t, GhostSides sides,
+                PcgScalars* scalars, double* partials, unsigned* counter, hipStream_t s);
 // mgp_residual_restrict ("mgp_residual_restrict"): mg_residual_restrict for a
 // coarse tile of (width / 2) x (height / 2): fine residuals outside the core
 // count as 0 (on an even side the last coarse cell's far neighbours), and the
 // residual reads the reflected ghost of a reflecting FINE level. The expression
 // and order of mg_residual_restrict.
 template <typename T>
-void mgp_residual_restrict(const T* u, const T* src, const TileGeom& g, bool reflect_rows, bool reflect_cols,
-                           T* coarse_src, const TileGeom& gc, Stencil5Coeffs c, hipStream_t s);
+void mgp_residual_restrict(const T* u, const T* src, const TileGeom& g, GhostSides sides, T* coarse_src,
+                           const TileGeom& gc, Stencil5Coeffs c, hipStream_t s);
 // mgp_prolong_add ("mgp_prolong_add"): mg_prolong_add's kernel (e = 0 outside
 // the coarse core by index) for a coarse tile of (width / 2) x (height / 2).
 template <typename T>
-void mgp_prolong_add(const T* e, const TileGeom& gc, T* u, const TileGeom& g, hipStream_t s);
+void mgp_prolong_add(const T* e, const TileGeom& gc, T* u, const TileGeom& g, hipStream_t s, GhostSides sides = {});
 // mgp_coarse_solve ("mgp_coarse_solve"): mg_coarse_solve with the flags: the
 // ghost row / column of a reflecting side is minus the last core row / column
 // at every sweep (minus zero at the start). With `scalars` (a single-level
 // preconditioner) it also sums src * e and writes rz and beta as mgp_smooth does.
 template <typename T>
-void mgp_coarse_solve(const T* src, T* e, const TileGeom& g, const MgSweepTable& t, int repeats, bool reflect_rows,
-                      bool reflect_cols, PcgScalars* scalars, hipStream_t s);
+void mgp_coarse_solve(const T* src, T* e, const TileGeom& g, const MgSweepTable& t, int repeats, GhostSides sides,
+                      PcgScalars* scalars, hipStream_t s);
 const char* last_pcg_dispatch();
 
 // Whether work on stream b runs while a kernel on stream a still runs (the two

@@ -24,6 +24,13 @@
 // c0_k = 1 - 4 c1 - 4^k sigma = c0 - (4^k - 1) sigma, and the coarse right-hand
 // side stays 4 R r. |sigma| <= 1e-12 (mg_check_operator's bound) counts as 0, so
 // the pure Laplace weights run the same doubles on every level.
+//
+// Neumann sides (cg.hpp's GhostSides; docs/ARCHITECTURE.md "Neumann sides"):
+// every level carries four ghost codes. Level 0 has the solve's (ring or
+// mirror). Near sides (top, left) of a coarse level inherit the kind. A far side
+// (bottom, right) is a mirror on every level when the finest level's is,
+// whatever the parity; otherwise the rule above: reflect under an even parent,
+// else ring. reflect_rows is bottom == -1 and reflect_cols is right == -1.
 #pragma once
 
 #include <cmath>
@@ -66,7 +73,23 @@ struct PcgLevel {
   bool reflect_rows = false;  // the ghost row `height` reads as minus row height - 1
   bool reflect_cols = false;  // the ghost column `width` reads as minus column width - 1
   double c0 = 0.0;            // c_center of this level
+  GhostSides sides;           // the four ghost codes; bottom == -1 <=> reflect_rows, right == -1 <=> reflect_cols
 };
+
+// A level from its flags and codes: a far code of 0 under a set flag becomes -1.
+inline PcgLevel pcg_level_of(long long w, long long h, bool reflect_rows, bool reflect_cols, double c0,
+                             GhostSides sides = {}) {
+  if (reflect_rows && sides.bottom == kGhostRing) sides.bottom = kGhostReflect;
+  if (reflect_cols && sides.right == kGhostRing) sides.right = kGhostReflect;
+  PcgLevel l;
+  l.width = w;
+  l.height = h;
+  l.reflect_rows = sides.bottom == kGhostReflect;
+  l.reflect_cols = sides.right == kGhostReflect;
+  l.c0 = c0;
+  l.sides = sides;
+  return l;
+}
 
 inline bool pcg_can_coarsen(long long w, long long h) {
   return (w > h ? w : h) > kMgCoarsenAbove && (w < h ? w : h) >= 2;
@@ -75,18 +98,22 @@ inline bool pcg_can_coarsen(long long w, long long h) {
 // Finest level first. Throws std::invalid_argument when the grid is empty, the
 // weights are not CG's or the coarsening stops above kMgCoarsestMax (only very
 // thin grids do; they are well conditioned).
-inline std::vector<PcgLevel> pcg_plan_levels(long long w, long long h, double c0, double c1) {
+inline std::vector<PcgLevel> pcg_plan_levels(long long w, long long h, double c0, double c1, GhostSides sides = {}) {
   if (w < 1 || h < 1) throw std::invalid_argument("preconditioned CG: the grid must be non-empty");
-  cg_check_operator(c0, c1);
+  cg_check_sides(c0, c1, sides);
   double sigma = 1.0 - c0 - 4.0 * c1;
   if (std::fabs(sigma) <= 1e-12) sigma = 0.0;
   std::vector<PcgLevel> lv;
-  lv.push_back({w, h, false, false, c0});
+  lv.push_back(pcg_level_of(w, h, false, false, c0, sides));
   double scale = 1.0;  // 4^k
   while (pcg_can_coarsen(lv.back().width, lv.back().height)) {
     const PcgLevel f = lv.back();
     scale *= 4.0;
-    lv.push_back({f.width / 2, f.height / 2, f.height % 2 == 0, f.width % 2 == 0, c0 - (scale - 1.0) * sigma});
+    const bool mirror_rows = sides.bottom == kGhostMirror, mirror_cols = sides.right == kGhostMirror;
+    lv.push_back(pcg_level_of(f.width / 2, f.height / 2, !mirror_rows && f.height % 2 == 0,
+                              !mirror_cols && f.width % 2 == 0, c0 - (scale - 1.0) * sigma,
+                              GhostSides{sides.top, mirror_rows ? kGhostMirror : kGhostRing, sides.left,
+                                         mirror_cols ? kGhostMirror : kGhostRing}));
   }
   const PcgLevel c = lv.back();
   if (c.width > kMgCoarsestMax || c.height > kMgCoarsestMax) {
@@ -157,7 +184,27 @@ inline LevelTable chebyshev_cycle_interval(double a, double b, double c_center, 
 // diagonal, a positive semi-definite term: the lower end still holds, and the
 // upper end becomes the Gershgorin bound 1 - c0 + 4 c1, which reflecting rows
 // still meet (diagonal 1 - c0 + c1, three neighbours of weight c1 at most).
+//
+// A level with a mirror side: a = 1 - c0 - c1 (mu_x + mu_y) with mu the largest
+// eigenvalue of the 1-D neighbour matrix of n cells under its two end codes
+// (pcg_axis_mu: exact, the operator is a Kronecker sum), b the Gershgorin bound.
+inline double pcg_axis_mu(long long n, int s, int t) {
+  const double pi = 3.14159265358979323846;
+  const int mirrors = (s == kGhostMirror) + (t == kGhostMirror), reflects = (s == kGhostReflect) + (t == kGhostReflect);
+  const double dn = double(n);
+  if (mirrors == 0 && reflects == 0) return 2.0 * std::cos(pi / (dn + 1.0));
+  if (mirrors == 1 && reflects == 0) return 2.0 * std::cos(pi / (2.0 * dn + 1.0));
+  if (mirrors == 2) return 2.0;
+  if (mirrors == 0 && reflects == 1) return 2.0 * std::cos(2.0 * pi / (2.0 * dn + 1.0));
+  if (mirrors == 1 && reflects == 1) return 2.0 * std::cos(pi / (2.0 * dn));
+  return 2.0 * std::cos(pi / dn);  // reflect, reflect
+}
+
 inline RelaxSpectrum pcg_coarse_interval(const PcgLevel& l, double c1) {
+  if (l.sides.any_mirror()) {
+    const double mu = pcg_axis_mu(l.width, l.sides.left, l.sides.right) + pcg_axis_mu(l.height, l.sides.top, l.sides.bottom);
+    return {1.0 - l.c0 - c1 * mu, 1.0 - l.c0 + 4.0 * c1};
+  }
   RelaxSpectrum sp = relaxation_spectrum(l.width, l.height, l.c0, c1);
   if (l.reflect_rows || l.reflect_cols) sp.b = 1.0 - l.c0 + 4.0 * c1;
   return sp;
@@ -168,10 +215,18 @@ inline RelaxSpectrum pcg_coarse_interval(const PcgLevel& l, double c1) {
 // pcg_coarse_interval (a Chebyshev polynomial grows outside its interval, and a
 // reflecting level has eigenvalues above relaxation_spectrum's upper end).
 inline MgCoarsePlan pcg_coarse_plan(const PcgLevel& l, double c1, double coarse_reduction) {
-  if (!l.reflect_rows && !l.reflect_cols) return mg_coarse_plan(l.width, l.height, l.c0, c1, coarse_reduction);
+  if (!l.reflect_rows && !l.reflect_cols && !l.sides.any_mirror())
+    return mg_coarse_plan(l.width, l.height, l.c0, c1, coarse_reduction);
   if (!(coarse_reduction > 0.0) || !(coarse_reduction < 1.0))
     throw std::invalid_argument("preconditioned CG: coarse_reduction must be in (0, 1)");
   const RelaxSpectrum sp = pcg_coarse_interval(l, c1);
+  if (!(sp.a > 0.0)) {
+    std::ostringstream os;
+    os.precision(17);
+    os << "preconditioned CG: the coarsest level's operator is singular (lower spectrum end " << sp.a << "): with all "
+       << "four sides Neumann the operator needs screening (c_center + 4 c_neighbor < 1), or one side held fixed";
+    throw std::invalid_argument(os.str());
+  }
   const LevelTable t = chebyshev_cycle_interval(sp.a, sp.b, l.c0, c1, kMgCoarseLevels);
   MgCoarsePlan p;
   p.table.n = t.n;
@@ -194,7 +249,12 @@ inline MgCoarsePlan pcg_coarse_plan(const PcgLevel& l, double c1, double coarse_
     r *= p.rho;
     ++p.repeats;
     if (p.repeats > kMgMaxCoarseRepeats)
-      throw std::invalid_argument("preconditioned CG: the coarse solve needs too many cycles");
+      throw std::invalid_argument(
+          l.sides.all_mirror()
+              ? "preconditioned CG: the coarse solve needs too many cycles: with all four sides Neumann and so little "
+                "screening the coarsest operator is nearly singular (constants are almost in its null space); hold one "
+                "side fixed or use a larger 1 - c_center - 4 c_neighbor"
+              : "preconditioned CG: the coarse solve needs too many cycles");
   }
   return p;
 }

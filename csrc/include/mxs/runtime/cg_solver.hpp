@@ -16,6 +16,11 @@
 // that is above tol the solve restarts from cg_start with the iterations
 // already spent counted, and after kCgMaxRestarts restarts it ends "stalled"
 // (the element type's floor).
+//
+// cfg.neumann names the Neumann sides (mxs/kernels/cg.hpp "GhostSides"): the
+// kernels then read the ghost of such a side as edge + ring (cg_start) or as
+// the edge cell of the direction itself (cg_apply), and the true residual is
+// that of the same operator. With none the launches are those of before.
 #pragma once
 
 #include <string>
@@ -30,6 +35,10 @@ struct CgConfig {
   index_t width = 0, height = 0;
   double c_center = 0.2, c_neighbor = 0.2;
   bool graph = true;
+  // The Neumann sides by name (top, bottom, left, right); every other side is
+  // Dirichlet. On a Neumann side the ring holds the prescribed outward
+  // difference d = u_ghost - u_edge (0: insulated) and the ghost reads edge + d.
+  std::vector<std::string> neumann;
 };
 
 struct CgResidual {
@@ -72,6 +81,9 @@ class CgSolver {
   void set_field(const T* tile);
   void field(T* tile);
   // Norms of the true residual (A u + g) - u: stencil5_residual with the source.
+  // With a Neumann side it is cg_start's residual (the ghost is edge + ring),
+  // taken into the scratch tiles q and p[1] and a scalar block of its own; a
+  // solve in progress must not call it.
   CgResidual residual();
   CgSolve solve(double tol, int max_iters, const std::string& norm, int check_every);
   // The device scalar block as it stands (a synchronising read).
@@ -86,9 +98,10 @@ class CgSolver {
   kernels::CgScalars read_scalars();
 
   CgConfig cfg_;
+  kernels::GhostSides sides_;
   TileGeom geom_;
   DeviceBuffer<T> u_, g_, r_, q_, p_[2];
-  DeviceBuffer<kernels::CgScalars> scalars_;
+  DeviceBuffer<kernels::CgScalars> scalars_, residual_scalars_;
   DeviceBuffer<double> partials_, residual_buf_;
   DeviceBuffer<unsigned> counter_, residual_counter_;
   PinnedBuffer<kernels::CgScalars> scalars_host_;

@@ -15,6 +15,10 @@
 // the p ping-pong closes); eager launches give the same bits. A reported
 // convergence is confirmed on the true residual, else a restart (at most
 // kCgMaxRestarts, then "stalled").
+//
+// cfg.neumann names the Neumann sides: pcg_start, pcg_apply and the true
+// residual follow CgSolver, and every level of the preconditioner carries its
+// ghost codes (mxs/kernels/pcg.hpp), mirrored transfers included.
 #pragma once
 
 #include <string>
@@ -33,6 +37,7 @@ struct PcgConfig {
   double smoother_omega = 0.8;
   double coarse_reduction = 1e-3;
   bool graph = true;
+  std::vector<std::string> neumann;  // CgConfig::neumann: the Neumann sides by name
 };
 
 template <typename T>
@@ -72,12 +77,13 @@ class PcgSolver {
   kernels::PcgScalars read_scalars();
 
   PcgConfig cfg_;
+  kernels::GhostSides sides_;
   TileGeom geom_;
   std::vector<kernels::PcgLevel> plan_;
   kernels::MgCoarsePlan coarse_;
   std::vector<Level> lv_;
   DeviceBuffer<T> u_, g_, r_, q_, p_[2];
-  DeviceBuffer<kernels::PcgScalars> scalars_;
+  DeviceBuffer<kernels::PcgScalars> scalars_, residual_scalars_;
   DeviceBuffer<double> partials_, residual_buf_;
   DeviceBuffer<unsigned> counter_, residual_counter_;
   PinnedBuffer<kernels::PcgScalars> scalars_host_;

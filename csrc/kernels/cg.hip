@@ -58,6 +58,8 @@ constexpr int kCh = 4;         // rows per chunk: row loads in flight per wave a
 // .. 8192^2, 1 per CU takes 0.50 .. 0.93 of the time of 4 per CU and more are
 // slower still (docs/PERF.md "Conjugate gradients").
 constexpr int kCgWgsPerCu = 1;
+// The mirror (Neumann) sides of a launch as one kernel argument.
+constexpr int kMirrorTop = 1, kMirrorBottom = 2, kMirrorLeft = 4, kMirrorRight = 8;
 
 std::atomic<const char*> g_last_cg{""};
 
@@ -169,11 +171,12 @@ struct Edge {
 
 // ------------------------------------------------------------------ cg_start
 // S: CgScalars (cg_*) or PcgScalars (pcg_*: no first direction is stored, rz = 0).
-template <typename T, typename S>
+// NEU: some side is a mirror (`mirror`: kMirrorTop | ...); without it the code is the ring-only kernel's.
+template <typename T, typename S, bool NEU>
 __global__ __launch_bounds__(kCgBlock) void cg_start_kernel(const T* __restrict__ u, const T* __restrict__ g,
                                                             T* __restrict__ r, T* __restrict__ p, index_t pitch,
                                                             index_t core_off, index_t W, index_t H, unsigned gx,
-                                                            index_t band_rows, T c0, T c1, int vec_ok, S* sc,
+                                                            index_t band_rows, T c0, T c1, int vec_ok, int mirror, S* sc,
                                                             double* partials, unsigned* counter) {
   constexpr bool kPcg = std::is_same<S, PcgScalars>::value;
   constexpr int N = CgVec<T>::N;
@@ -234,7 +237,17 @@ __global__ __launch_bounds__(kCgBlock) void cg_start_kernel(const T* __restrict_
           for (int i = 0; i < N; ++i) {
             const T w = i == 0 ? left : mid[i > 0 ? i - 1 : 0];
             const T ea = i == N - 1 ? right : mid[i < N - 1 ? i + 1 : 0];
-            T res = fma_t<T>(c1, (up[i] + dn[k][i]) + (w + ea), c0 * mid[i]);
+            T res;
+            if constexpr (NEU) {  // a mirror ghost is edge + ring (the ring holds d), one addition
+              const T c = mid[i];
+              const T nn = (mirror & kMirrorTop) && y + k == 0 ? c + up[i] : up[i];
+              const T ss = (mirror & kMirrorBottom) && y + k == H - 1 ? c + dn[k][i] : dn[k][i];
+              const T ww = (mirror & kMirrorLeft) && L.x + i == 0 ? c + w : w;
+              const T ee = (mirror & kMirrorRight) && L.x + i == W - 1 ? c + ea : ea;
+              res = fma_t<T>(c1, (nn + ss) + (ww + ee), c0 * c);
+            } else {
+              res = fma_t<T>(c1, (up[i] + dn[k][i]) + (w + ea), c0 * mid[i]);
+            }
             res = res + gmid[i];
             res = res - mid[i];
             res = i < nvalid ? res : T(0);  // a select: whatever sits past the core never enters
@@ -268,12 +281,13 @@ __global__ __launch_bounds__(kCgBlock) void cg_start_kernel(const T* __restrict_
 
 // ------------------------------------------------------------------ cg_apply
 // S: CgScalars (alpha = rr / pq) or PcgScalars (r is z = M r, alpha = rz / pq).
-template <typename T, typename S>
+// NEU: on a mirror side the ghost operand is the edge value of p_new itself (the ring is folded into b).
+template <typename T, typename S, bool NEU>
 __global__ __launch_bounds__(kCgBlock) void cg_apply_kernel(const T* __restrict__ r, const T* __restrict__ po,
                                                             T* __restrict__ pn, T* __restrict__ q, index_t pitch,
                                                             index_t core_off, index_t W, index_t H, unsigned gx,
-                                                            index_t band_rows, T diag, T nc1, int vec_ok, S* sc,
-                                                            double* partials, unsigned* counter) {
+                                                            index_t band_rows, T diag, T nc1, int vec_ok, int mirror,
+                                                            S* sc, double* partials, unsigned* counter) {
   constexpr int N = CgVec<T>::N;
   using V = typename CgVec<T>::type;
   if (sc->status != kCgRunning) return;  // grid-uniform: nothing is stored, the ticket stays 0
@@ -352,7 +366,17 @@ __global__ __launch_bounds__(kCgBlock) void cg_apply_kernel(const T* __restrict_
           for (int i = 0; i < N; ++i) {
             const T w = i == 0 ? left : mid[i > 0 ? i - 1 : 0];
             const T ea = i == N - 1 ? right : mid[i < N - 1 ? i + 1 : 0];
-            T res = fma_t<T>(nc1, (up[i] + dn[i]) + (w + ea), diag * mid[i]);
+            T res;
+            if constexpr (NEU) {  // only the global edges mirror, never a band or strip boundary
+              const T c = mid[i];
+              const T nn = (mirror & kMirrorTop) && y + k == 0 ? c : up[i];
+              const T ss = (mirror & kMirrorBottom) && y + k == H - 1 ? c : dn[i];
+              const T ww = (mirror & kMirrorLeft) && L.x + i == 0 ? c : w;
+              const T ee = (mirror & kMirrorRight) && L.x + i == W - 1 ? c : ea;
+              res = fma_t<T>(nc1, (nn + ss) + (ww + ee), diag * c);
+            } else {
+              res = fma_t<T>(nc1, (up[i] + dn[i]) + (w + ea), diag * mid[i]);
+            }
             res = i < nvalid ? res : T(0);
             out[i] = res;
             acc = __builtin_fma(double(mid[i]), double(res), acc);
@@ -472,6 +496,14 @@ bool aligned16(const T* tile, const TileGeom& g) {
   return reinterpret_cast<std::uintptr_t>(tile + g.core_offset()) % 16 == 0;
 }
 
+// The sides of a CG launch are the solve's: ring or mirror.
+int mirror_mask(const char* who, const GhostSides& sd) {
+  for (int code : {sd.top, sd.bottom, sd.left, sd.right})
+    MXS_CHECK(code == kGhostRing || code == kGhostMirror, who << ": a side is ring (0) or mirror (+1), got " << code);
+  return (sd.top ? kMirrorTop : 0) | (sd.bottom ? kMirrorBottom : 0) | (sd.left ? kMirrorLeft : 0) |
+         (sd.right ? kMirrorRight : 0);
+}
+
 // The checks every launcher shares; returns the grid.
 template <typename T>
 CgGrid check(const char* who, const TileGeom& g, std::initializer_list<const T*> tiles, const void* scalars,
@@ -502,22 +534,25 @@ int cg_grid_size(const TileGeom& g) {
 
 template <typename T>
 void cg_start(const T* u, const T* g, T* r, T* p, const TileGeom& geom, Stencil5Coeffs c, CgScalars* scalars,
-              double* partials, unsigned* counter, hipStream_t s) {
+              double* partials, unsigned* counter, hipStream_t s, GhostSides sides) {
   const CgGrid cg = check<T>("cg_start", geom, {u, g, r, p}, scalars, partials, counter);
   MXS_CHECK(u != r && u != p && g != r && g != p && r != p, "cg_start: u, g, r and p must be four tiles (r != p)");
   constexpr int N = CgVec<T>::N;
   const int vec_ok = geom.pitch % N == 0 && aligned16(u, geom) && aligned16(g, geom) && aligned16(r, geom) &&
                      aligned16(p, geom);
-  cg_start_kernel<T, CgScalars><<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(
-      u, g, r, p, geom.pitch, geom.core_offset(), geom.width, geom.height, cg.gx, cg.band_rows, T(c.center),
-      T(c.neighbor), vec_ok, scalars, partials, counter);
+  const int mirror = mirror_mask("cg_start", sides);
+  auto* kernel = mirror ? cg_start_kernel<T, CgScalars, true> : cg_start_kernel<T, CgScalars, false>;
+  kernel<<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(u, g, r, p, geom.pitch, geom.core_offset(), geom.width,
+                                                                  geom.height, cg.gx, cg.band_rows, T(c.center),
+                                                                  T(c.neighbor), vec_ok, mirror, scalars, partials,
+                                                                  counter);
   g_last_cg = "cg_start";
   MXS_HIP_CHECK_LAUNCH();
 }
 
 template <typename T>
 void cg_apply(const T* r, const T* p_old, T* p_new, T* q, const TileGeom& geom, Stencil5Coeffs c, CgScalars* scalars,
-              double* partials, unsigned* counter, hipStream_t s) {
+              double* partials, unsigned* counter, hipStream_t s, GhostSides sides) {
   const CgGrid cg = check<T>("cg_apply", geom, {r, p_old, p_new, q}, scalars, partials, counter);
   MXS_CHECK(p_old != p_new, "cg_apply: p_old != p_new (neighbouring workgroups still read p_old: pass the other "
                             "buffer of the ping-pong pair)");
@@ -525,9 +560,12 @@ void cg_apply(const T* r, const T* p_old, T* p_new, T* q, const TileGeom& geom, 
   constexpr int N = CgVec<T>::N;
   const int vec_ok = geom.pitch % N == 0 && aligned16(r, geom) && aligned16(p_old, geom) && aligned16(p_new, geom) &&
                      aligned16(q, geom);
-  cg_apply_kernel<T, CgScalars><<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(
-      r, p_old, p_new, q, geom.pitch, geom.core_offset(), geom.width, geom.height, cg.gx, cg.band_rows,
-      T(1.0 - c.center), T(-c.neighbor), vec_ok, scalars, partials, counter);
+  const int mirror = mirror_mask("cg_apply", sides);
+  auto* kernel = mirror ? cg_apply_kernel<T, CgScalars, true> : cg_apply_kernel<T, CgScalars, false>;
+  kernel<<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(r, p_old, p_new, q, geom.pitch, geom.core_offset(),
+                                                                  geom.width, geom.height, cg.gx, cg.band_rows,
+                                                                  T(1.0 - c.center), T(-c.neighbor), vec_ok, mirror,
+                                                                  scalars, partials, counter);
   g_last_cg = "cg_apply";
   MXS_HIP_CHECK_LAUNCH();
 }
@@ -550,21 +588,24 @@ void cg_update(T* u, T* r, const T* p, const T* q, const TileGeom& geom, CgScala
 // -------------------------------------------------------- preconditioned CG
 template <typename T>
 void pcg_start(const T* u, const T* g, T* r, const TileGeom& geom, Stencil5Coeffs c, PcgScalars* scalars,
-               double* partials, unsigned* counter, hipStream_t s) {
+               double* partials, unsigned* counter, hipStream_t s, GhostSides sides) {
   const CgGrid cg = check<T>("pcg_start", geom, {u, g, r}, scalars, partials, counter);
   MXS_CHECK(u != r && g != r && u != g, "pcg_start: u, g and r must be three tiles");
   constexpr int N = CgVec<T>::N;
   const int vec_ok = geom.pitch % N == 0 && aligned16(u, geom) && aligned16(g, geom) && aligned16(r, geom);
-  cg_start_kernel<T, PcgScalars><<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(
-      u, g, r, static_cast<T*>(nullptr), geom.pitch, geom.core_offset(), geom.width, geom.height, cg.gx, cg.band_rows,
-      T(c.center), T(c.neighbor), vec_ok, scalars, partials, counter);
+  const int mirror = mirror_mask("pcg_start", sides);
+  auto* kernel = mirror ? cg_start_kernel<T, PcgScalars, true> : cg_start_kernel<T, PcgScalars, false>;
+  kernel<<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(u, g, r, static_cast<T*>(nullptr), geom.pitch,
+                                                                  geom.core_offset(), geom.width, geom.height, cg.gx,
+                                                                  cg.band_rows, T(c.center), T(c.neighbor), vec_ok, mirror,
+                                                                  scalars, partials, counter);
   g_last_cg = "pcg_start";
   MXS_HIP_CHECK_LAUNCH();
 }
 
 template <typename T>
 void pcg_apply(const T* z, const T* p_old, T* p_new, T* q, const TileGeom& geom, Stencil5Coeffs c, PcgScalars* scalars,
-               double* partials, unsigned* counter, hipStream_t s) {
+               double* partials, unsigned* counter, hipStream_t s, GhostSides sides) {
   const CgGrid cg = check<T>("pcg_apply", geom, {z, p_old, p_new, q}, scalars, partials, counter);
   MXS_CHECK(p_old != p_new, "pcg_apply: p_old != p_new (neighbouring workgroups still read p_old: pass the other "
                             "buffer of the ping-pong pair)");
@@ -572,9 +613,12 @@ void pcg_apply(const T* z, const T* p_old, T* p_new, T* q, const TileGeom& geom,
   constexpr int N = CgVec<T>::N;
   const int vec_ok = geom.pitch % N == 0 && aligned16(z, geom) && aligned16(p_old, geom) && aligned16(p_new, geom) &&
                      aligned16(q, geom);
-  cg_apply_kernel<T, PcgScalars><<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(
-      z, p_old, p_new, q, geom.pitch, geom.core_offset(), geom.width, geom.height, cg.gx, cg.band_rows,
-      T(1.0 - c.center), T(-c.neighbor), vec_ok, scalars, partials, counter);
+  const int mirror = mirror_mask("pcg_apply", sides);
+  auto* kernel = mirror ? cg_apply_kernel<T, PcgScalars, true> : cg_apply_kernel<T, PcgScalars, false>;
+  kernel<<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(z, p_old, p_new, q, geom.pitch, geom.core_offset(),
+                                                                  geom.width, geom.height, cg.gx, cg.band_rows,
+                                                                  T(1.0 - c.center), T(-c.neighbor), vec_ok, mirror,
+                                                                  scalars, partials, counter);
   g_last_cg = "pcg_apply";
   MXS_HIP_CHECK_LAUNCH();
 }
@@ -596,14 +640,14 @@ void pcg_update(T* u, T* r, const T* p, const T* q, const TileGeom& geom, PcgSca
 
 #define MXS_CG_INSTANTIATE(T)                                                                                       \
   template void cg_start<T>(const T*, const T*, T*, T*, const TileGeom&, Stencil5Coeffs, CgScalars*, double*,       \
-                            unsigned*, hipStream_t);                                                                \
+                            unsigned*, hipStream_t, GhostSides);                                                    \
   template void cg_apply<T>(const T*, const T*, T*, T*, const TileGeom&, Stencil5Coeffs, CgScalars*, double*,       \
-                            unsigned*, hipStream_t);                                                                \
+                            unsigned*, hipStream_t, GhostSides);                                                    \
   template void cg_update<T>(T*, T*, const T*, const T*, const TileGeom&, CgScalars*, double*, unsigned*, hipStream_t); \
   template void pcg_start<T>(const T*, const T*, T*, const TileGeom&, Stencil5Coeffs, PcgScalars*, double*, unsigned*, \
-                             hipStream_t);                                                                             \
+                             hipStream_t, GhostSides);                                                                 \
   template void pcg_apply<T>(const T*, const T*, T*, T*, const TileGeom&, Stencil5Coeffs, PcgScalars*, double*,       \
-                             unsigned*, hipStream_t);                                                                  \
+                             unsigned*, hipStream_t, GhostSides);                                                      \
   template void pcg_update<T>(T*, T*, const T*, const T*, const TileGeom&, PcgScalars*, double*, unsigned*, hipStream_t);
 MXS_CG_INSTANTIATE(float)
 MXS_CG_INSTANTIATE(double)

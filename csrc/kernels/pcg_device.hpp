@@ -29,8 +29,26 @@ namespace detail {
 
 static_assert(kMgBlock == cgdev::kCgBlock, "the dot epilogue reduces over workgroups of kCgBlock threads");
 
+// A level's four ghost codes (cg.hpp's GhostSides) as a kernel argument: 0 the
+// ring, -1 reflect (minus the edge cell), +1 mirror (plus the edge cell).
+struct MgpSides {
+  int top, bottom, left, right;
+  // The code that governs ghost row gy (column gx); 0 for every other row (column).
+  __device__ __forceinline__ int row_code(index_t gy, index_t H) const { return gy == -1 ? top : (gy == H ? bottom : 0); }
+  __device__ __forceinline__ int col_code(index_t gx, index_t W) const { return gx == -1 ? left : (gx == W ? right : 0); }
+};
+
+// The ghost beside edge value v under a non-zero code: an exact negation or v itself.
+template <typename T>
+__device__ __forceinline__ T ghost_of(int code, T v) {
+  return code < 0 ? -v : v;
+}
+
 // ------------------------------------------------------------------ smoother
-// mg_smooth_kernel with reflect flags. The staged window holds the ghost row H
+// mg_smooth_kernel with ghost codes (reflect described here; a mirror side, near
+// or far, is the same with the other sign: the ghost row -1 / column -1 mirrors
+// core row 0 / column 0 and the ZERO start stages +0 there).
+// The staged window holds the ghost row H
 // (column W) of a reflecting side as minus the staged core row H - 1 (column
 // W - 1), never the tile's ring there. After sweep s the thread that advanced
 // a cell of the last core row (column) also writes its negation into the ghost
@@ -47,8 +65,8 @@ template <typename T, int NU, bool DOT, bool ZERO>
 __global__ __launch_bounds__(kMgBlock) void mgp_smooth_kernel(const T* __restrict__ in, T* __restrict__ out,
                                                               const T* __restrict__ gsrc, index_t pitch,
                                                               index_t core_off, index_t W, index_t H,
-                                                              MgSweeps<T, NU> tab, int reflect_rows, int reflect_cols,
-                                                              PcgScalars* sc, double* partials, unsigned* counter) {
+                                                              MgSweeps<T, NU> tab, MgpSides sd, PcgScalars* sc,
+                                                              double* partials, unsigned* counter) {
   constexpr int LW = kMgTw + 2 * NU, LH = kMgTh + 2 * NU;
   constexpr int LP = LW + 1;
   constexpr int IW = LW - 2, IH = LH - 2;
@@ -64,13 +82,13 @@ __global__ __launch_bounds__(kMgBlock) void mgp_smooth_kernel(const T* __restric
     const index_t gy = ty0 - NU + r, gx = tx0 - NU + c;
     T v = T(0);
     if (gy >= -1 && gy <= H && gx >= -1 && gx <= W) {
-      const bool grow = reflect_rows && gy == H, gcol = reflect_cols && gx == W;
-      if (!grow && !gcol) {
+      const int cy = sd.row_code(gy, H), cx = sd.col_code(gx, W);
+      if (cy == 0 && cx == 0) {
         if constexpr (!ZERO) v = in[core_off + gy * pitch + gx];
-      } else if (grow && !gcol) {
-        if (gx >= 0 && gx < W) v = ZERO ? -T(0) : -in[core_off + (H - 1) * pitch + gx];
-      } else if (gcol && !grow) {
-        if (gy >= 0 && gy < H) v = ZERO ? -T(0) : -in[core_off + gy * pitch + (W - 1)];
+      } else if (cy != 0 && cx == 0) {
+        if (gx >= 0 && gx < W) v = ghost_of<T>(cy, ZERO ? T(0) : in[core_off + (gy < 0 ? 0 : H - 1) * pitch + gx]);
+      } else if (cx != 0 && cy == 0) {
+        if (gy >= 0 && gy < H) v = ghost_of<T>(cx, ZERO ? T(0) : in[core_off + gy * pitch + (gx < 0 ? 0 : W - 1)]);
       }
     }
     buf[r * LP + c] = v;
@@ -120,8 +138,10 @@ __global__ __launch_bounds__(kMgBlock) void mgp_smooth_kernel(const T* __restric
         if (r > s && r < LH - 1 - s && c > s && c < LW - 1 - s) {
           buf[r * LP + c] = res[k];
           const index_t gy = ty0 - NU + r, gx = tx0 - NU + c;
-          if (reflect_rows && gy == H - 1) buf[(r + 1) * LP + c] = -res[k];
-          if (reflect_cols && gx == W - 1) buf[r * LP + c + 1] = -res[k];
+          if (sd.bottom && gy == H - 1) buf[(r + 1) * LP + c] = ghost_of<T>(sd.bottom, res[k]);
+          if (sd.right && gx == W - 1) buf[r * LP + c + 1] = ghost_of<T>(sd.right, res[k]);
+          if (sd.top && gy == 0) buf[(r - 1) * LP + c] = ghost_of<T>(sd.top, res[k]);
+          if (sd.left && gx == 0) buf[r * LP + c - 1] = ghost_of<T>(sd.left, res[k]);
           if constexpr (DOT) {
             // The output tile's cells (live: inside the core), at the last sweep.
             if (s == NU - 1 && r >= NU && r < NU + kMgTh && c >= NU && c < NU + kMgTw)
@@ -159,8 +179,7 @@ template <typename T>
 __global__ __launch_bounds__(kMgBlock) void mgp_residual_restrict_kernel(const T* __restrict__ u,
                                                                          const T* __restrict__ gsrc, index_t pitch,
                                                                          index_t core_off, index_t W, index_t H,
-                                                                         int reflect_rows, int reflect_cols,
-                                                                         T* __restrict__ gc, index_t cpitch,
+                                                                         MgpSides sd, T* __restrict__ gc, index_t cpitch,
                                                                          index_t ccore_off, index_t CW, index_t CH,
                                                                          T c0, T c1) {
   constexpr int RW = 2 * kMgCw + 1, RH = 2 * kMgCh + 1;
@@ -178,13 +197,13 @@ __global__ __launch_bounds__(kMgBlock) void mgp_residual_restrict_kernel(const T
     const index_t gy = fy0 - 1 + r, gx = fx0 - 1 + c;  // >= -1 always
     T v = T(0);
     if (gy <= H && gx <= W) {
-      const bool grow = reflect_rows && gy == H, gcol = reflect_cols && gx == W;
-      if (!grow && !gcol) {
+      const int cy = sd.row_code(gy, H), cx = sd.col_code(gx, W);
+      if (cy == 0 && cx == 0) {
         v = u[core_off + gy * pitch + gx];
-      } else if (grow && !gcol) {
-        if (gx >= 0 && gx < W) v = -u[core_off + (H - 1) * pitch + gx];
-      } else if (gcol && !grow) {
-        if (gy >= 0 && gy < H) v = -u[core_off + gy * pitch + (W - 1)];
+      } else if (cy != 0 && cx == 0) {
+        if (gx >= 0 && gx < W) v = ghost_of<T>(cy, u[core_off + (gy < 0 ? 0 : H - 1) * pitch + gx]);
+      } else if (cx != 0 && cy == 0) {
+        if (gy >= 0 && gy < H) v = ghost_of<T>(cx, u[core_off + gy * pitch + (gx < 0 ? 0 : W - 1)]);
       }
     }
     ub[r * UP + c] = v;
@@ -199,6 +218,10 @@ __global__ __launch_bounds__(kMgBlock) void mgp_residual_restrict_kernel(const T
       const T v = ub[b];
       const T a = mg_fma<T>(c1, (ub[b - UP] + ub[b + UP]) + (ub[b - 1] + ub[b + 1]), c0 * v);
       res = (a + gsrc[core_off + gy * pitch + gx]) - v;
+      // The transpose of the mirrored prolongation: a fine row / column whose outer
+      // coarse neighbour is a mirror ghost counts twice (an exact doubling).
+      if ((sd.top > 0 && gy == 0) || (sd.bottom > 0 && gy == H - 1 && (H & 1))) res = res + res;
+      if ((sd.left > 0 && gx == 0) || (sd.right > 0 && gx == W - 1 && (W & 1))) res = res + res;
     }
     rb[r * RP + c] = res;
   }
@@ -214,8 +237,42 @@ __global__ __launch_bounds__(kMgBlock) void mgp_residual_restrict_kernel(const T
   }
 }
 
+// -------------------------------------------------------------- prolongation
+// mg_prolong_add_kernel where a coarse ghost on a mirror side equals the
+// mirrored coarse cell: at(i, j) clamps i = -1 -> 0 on a mirror top and i = CH ->
+// CH - 1 on a mirror bottom, and the same for columns; on ring / reflect sides
+// it stays 0. The expressions are mg_prolong_add_kernel's.
+template <typename T>
+__global__ __launch_bounds__(kMgBlock) void mgp_prolong_add_kernel(const T* __restrict__ e, index_t cpitch,
+                                                                   index_t ccore_off, index_t CW, index_t CH,
+                                                                   T* __restrict__ u, index_t pitch, index_t core_off,
+                                                                   index_t W, index_t H, MgpSides sd) {
+  const index_t x = index_t(blockIdx.x) * 64 + (threadIdx.x & 63);
+  const index_t y = index_t(blockIdx.y) * 4 + (threadIdx.x >> 6);
+  if (x >= W || y >= H) return;
+  const index_t I = y >> 1, J = x >> 1;
+  auto at = [&](index_t i, index_t j) -> T {
+    if (sd.top > 0 && i < 0) i = 0;
+    if (sd.bottom > 0 && i >= CH) i = CH - 1;
+    if (sd.left > 0 && j < 0) j = 0;
+    if (sd.right > 0 && j >= CW) j = CW - 1;
+    return (i >= 0 && i < CH && j >= 0 && j < CW) ? e[ccore_off + i * cpitch + j] : T(0);
+  };
+  T p;
+  if (y & 1) {
+    if (x & 1) p = at(I, J);
+    else p = T(0.5) * (at(I, J - 1) + at(I, J));
+  } else {
+    if (x & 1) p = T(0.5) * (at(I - 1, J) + at(I, J));
+    else p = T(0.25) * ((at(I - 1, J - 1) + at(I, J - 1)) + (at(I - 1, J) + at(I, J)));
+  }
+  T* q = u + core_off + y * pitch + x;
+  *q = *q + p;
+}
+
 // -------------------------------------------------------------- coarse solve
-// mg_coarse_solve_kernel with reflect flags: both LDS buffers keep the ghost row
+// mg_coarse_solve_kernel with ghost codes (a mirror side like a reflecting one,
+// with +0 at the start and the advanced edge cell itself afterwards): both LDS buffers keep the ghost row
 // H (column W) of a reflecting side as minus the last core row (column): -0 at
 // the start, then written by the thread that advances the mirrored cell. With
 // `sc` it also sums src * e over the core and finishes like mgp_smooth's dot.
@@ -223,8 +280,7 @@ template <typename T>
 __global__ __launch_bounds__(kMgBlock) void mgp_coarse_solve_kernel(const T* __restrict__ gsrc, T* __restrict__ e,
                                                                     index_t pitch, index_t core_off, int W, int H,
                                                                     int repeats, MgSweeps<T, kMaxLevels> tab, int levels,
-                                                                    int reflect_rows, int reflect_cols,
-                                                                    PcgScalars* sc) {
+                                                                    MgpSides sd, PcgScalars* sc) {
   extern __shared__ __attribute__((aligned(16))) unsigned char mgp_smem[];
   const int P = W + 2, FULL = P * (H + 2), N = W * H;
   T* a = reinterpret_cast<T*>(mgp_smem);
@@ -234,8 +290,9 @@ __global__ __launch_bounds__(kMgBlock) void mgp_coarse_solve_kernel(const T* __r
   for (int i = tid; i < 2 * FULL; i += kMgBlock) {
     const int j = i < FULL ? i : i - FULL;
     const int r = j / P, c = j - r * P;  // ring included: core is 1..H, 1..W
-    const bool ghost = (reflect_rows && r == H + 1 && c >= 1 && c <= W) || (reflect_cols && c == W + 1 && r >= 1 && r <= H);
-    a[i] = ghost ? -T(0) : T(0);
+    const bool in_cols = c >= 1 && c <= W, in_rows = r >= 1 && r <= H;
+    const bool minus = (sd.bottom < 0 && r == H + 1 && in_cols) || (sd.right < 0 && c == W + 1 && in_rows);
+    a[i] = minus ? -T(0) : T(0);  // a mirror ghost starts at +0
   }
   for (int i = tid; i < N; i += kMgBlock) {
     const int r = i / W, c = i - r * W;
@@ -252,8 +309,10 @@ __global__ __launch_bounds__(kMgBlock) void mgp_coarse_solve_kernel(const T* __r
         const int q = (r + 1) * P + c + 1;
         const T v = mg_sweep<T>(cur[q], cur[q - P], cur[q + P], cur[q - 1], cur[q + 1], g[i], ce, nb, wt);
         nxt[q] = v;
-        if (reflect_rows && r == H - 1) nxt[q + P] = -v;
-        if (reflect_cols && c == W - 1) nxt[q + 1] = -v;
+        if (sd.bottom && r == H - 1) nxt[q + P] = ghost_of<T>(sd.bottom, v);
+        if (sd.right && c == W - 1) nxt[q + 1] = ghost_of<T>(sd.right, v);
+        if (sd.top && r == 0) nxt[q - P] = ghost_of<T>(sd.top, v);
+        if (sd.left && c == 0) nxt[q - 1] = ghost_of<T>(sd.left, v);
       }
       __syncthreads();
       T* t = cur;

@@ -41,13 +41,22 @@ detail::MgSweeps<T, N> sweeps_of(const MgSweepTable& t) {
   return k;
 }
 
+// A level's codes: near sides ring or mirror, far sides also reflect.
+detail::MgpSides sides_of(const GhostSides& sd, const char* who) {
+  MXS_CHECK((sd.top == kGhostRing || sd.top == kGhostMirror) && (sd.left == kGhostRing || sd.left == kGhostMirror),
+            who << ": a near side (top, left) is ring (0) or mirror (+1)");
+  MXS_CHECK(sd.bottom >= -1 && sd.bottom <= 1 && sd.right >= -1 && sd.right <= 1,
+            who << ": a far side (bottom, right) is ring (0), mirror (+1) or reflect (-1)");
+  return detail::MgpSides{sd.top, sd.bottom, sd.left, sd.right};
+}
+
 dim3 smooth_grid(const TileGeom& g) {
   return dim3(unsigned((g.width + detail::kMgTw - 1) / detail::kMgTw),
               unsigned((g.height + detail::kMgTh - 1) / detail::kMgTh));
 }
 
 template <typename T, int NU>
-void launch_smooth(const T* in, T* out, const T* src, const TileGeom& g, const MgSweepTable& t, bool rr, bool rc,
+void launch_smooth(const T* in, T* out, const T* src, const TileGeom& g, const MgSweepTable& t, detail::MgpSides sd,
                    PcgScalars* sc, double* partials, unsigned* counter, hipStream_t s) {
   const dim3 grid = smooth_grid(g);
   PcgScalars* no_sc = nullptr;
@@ -55,16 +64,15 @@ void launch_smooth(const T* in, T* out, const T* src, const TileGeom& g, const M
   unsigned* no_counter = nullptr;
   if (sc)  // the finest post-smooth: never from zero
     detail::mgp_smooth_kernel<T, NU, true, false><<<grid, detail::kMgBlock, 0, s>>>(
-        in, out, src, g.pitch, g.core_offset(), g.width, g.height, sweeps_of<T, NU>(t), int(rr), int(rc), sc, partials,
-        counter);
+        in, out, src, g.pitch, g.core_offset(), g.width, g.height, sweeps_of<T, NU>(t), sd, sc, partials, counter);
   else if (in == nullptr)
     detail::mgp_smooth_kernel<T, NU, false, true><<<grid, detail::kMgBlock, 0, s>>>(
-        in, out, src, g.pitch, g.core_offset(), g.width, g.height, sweeps_of<T, NU>(t), int(rr), int(rc), no_sc,
-        no_partials, no_counter);
+        in, out, src, g.pitch, g.core_offset(), g.width, g.height, sweeps_of<T, NU>(t), sd, no_sc, no_partials,
+        no_counter);
   else
     detail::mgp_smooth_kernel<T, NU, false, false><<<grid, detail::kMgBlock, 0, s>>>(
-        in, out, src, g.pitch, g.core_offset(), g.width, g.height, sweeps_of<T, NU>(t), int(rr), int(rc), no_sc,
-        no_partials, no_counter);
+        in, out, src, g.pitch, g.core_offset(), g.width, g.height, sweeps_of<T, NU>(t), sd, no_sc, no_partials,
+        no_counter);
 }
 
 }  // namespace
@@ -77,9 +85,10 @@ int mgp_smooth_grid_size(const TileGeom& g) {
 }
 
 template <typename T>
-void mgp_smooth(const T* u_in, T* u_out, const T* src, const TileGeom& g, const MgSweepTable& t, bool reflect_rows,
-                bool reflect_cols, PcgScalars* scalars, double* partials, unsigned* counter, hipStream_t s) {
+void mgp_smooth(const T* u_in, T* u_out, const T* src, const TileGeom& g, const MgSweepTable& t, GhostSides sides,
+                PcgScalars* scalars, double* partials, unsigned* counter, hipStream_t s) {
   check_tile(g, "mgp_smooth");
+  const detail::MgpSides sd = sides_of(sides, "mgp_smooth");
   MXS_CHECK(t.n >= 1 && t.n <= kMgMaxSmooth, "mgp_smooth: 1.." << kMgMaxSmooth << " sweeps per launch, got " << t.n);
   MXS_CHECK(u_out && src && u_in != u_out, "mgp_smooth: needs u_out and src, u_in != u_out");
   MXS_CHECK(u_in || !scalars, "mgp_smooth: a start from zero (u_in null) carries no dot epilogue");
@@ -92,46 +101,49 @@ void mgp_smooth(const T* u_in, T* u_out, const T* src, const TileGeom& g, const 
                   reinterpret_cast<std::uintptr_t>(counter) % sizeof(unsigned) == 0,
               "mgp_smooth: the scalar block, the partials and the ticket must be aligned");
   switch (t.n) {
-    case 1: launch_smooth<T, 1>(u_in, u_out, src, g, t, reflect_rows, reflect_cols, scalars, partials, counter, s); break;
-    case 2: launch_smooth<T, 2>(u_in, u_out, src, g, t, reflect_rows, reflect_cols, scalars, partials, counter, s); break;
-    case 3: launch_smooth<T, 3>(u_in, u_out, src, g, t, reflect_rows, reflect_cols, scalars, partials, counter, s); break;
-    default: launch_smooth<T, 4>(u_in, u_out, src, g, t, reflect_rows, reflect_cols, scalars, partials, counter, s); break;
+    case 1: launch_smooth<T, 1>(u_in, u_out, src, g, t, sd, scalars, partials, counter, s); break;
+    case 2: launch_smooth<T, 2>(u_in, u_out, src, g, t, sd, scalars, partials, counter, s); break;
+    case 3: launch_smooth<T, 3>(u_in, u_out, src, g, t, sd, scalars, partials, counter, s); break;
+    default: launch_smooth<T, 4>(u_in, u_out, src, g, t, sd, scalars, partials, counter, s); break;
   }
   g_last_pcg = scalars ? "mgp_smooth_dot" : (u_in ? "mgp_smooth" : "mgp_smooth_zero");
   MXS_HIP_CHECK_LAUNCH();
 }
 
 template <typename T>
-void mgp_residual_restrict(const T* u, const T* src, const TileGeom& g, bool reflect_rows, bool reflect_cols,
-                           T* coarse_src, const TileGeom& gc, Stencil5Coeffs c, hipStream_t s) {
+void mgp_residual_restrict(const T* u, const T* src, const TileGeom& g, GhostSides sides, T* coarse_src,
+                           const TileGeom& gc, Stencil5Coeffs c, hipStream_t s) {
   check_pair(g, gc, "mgp_residual_restrict");
+  const detail::MgpSides sd = sides_of(sides, "mgp_residual_restrict");
   MXS_CHECK(u && src && coarse_src, "mgp_residual_restrict: needs u, src and coarse_src");
   const dim3 grid(unsigned((gc.width + detail::kMgCw - 1) / detail::kMgCw),
                   unsigned((gc.height + detail::kMgCh - 1) / detail::kMgCh));
   MXS_CHECK(grid.y <= 65535, "mgp_residual_restrict: too many tile rows for one launch");
   detail::mgp_residual_restrict_kernel<T><<<grid, detail::kMgBlock, 0, s>>>(
-      u, src, g.pitch, g.core_offset(), g.width, g.height, int(reflect_rows), int(reflect_cols), coarse_src, gc.pitch,
-      gc.core_offset(), gc.width, gc.height, T(c.center), T(c.neighbor));
+      u, src, g.pitch, g.core_offset(), g.width, g.height, sd, coarse_src, gc.pitch, gc.core_offset(), gc.width,
+      gc.height, T(c.center), T(c.neighbor));
   g_last_pcg = "mgp_residual_restrict";
   MXS_HIP_CHECK_LAUNCH();
 }
 
 template <typename T>
-void mgp_prolong_add(const T* e, const TileGeom& gc, T* u, const TileGeom& g, hipStream_t s) {
+void mgp_prolong_add(const T* e, const TileGeom& gc, T* u, const TileGeom& g, hipStream_t s, GhostSides sides) {
   check_pair(g, gc, "mgp_prolong_add");
+  const detail::MgpSides sd = sides_of(sides, "mgp_prolong_add");
   MXS_CHECK(e && u, "mgp_prolong_add: needs e and u");
   const dim3 grid(unsigned((g.width + 63) / 64), unsigned((g.height + 3) / 4));
   MXS_CHECK(grid.y <= 65535, "mgp_prolong_add: too many rows for one launch");
-  detail::mg_prolong_add_kernel<T><<<grid, detail::kMgBlock, 0, s>>>(e, gc.pitch, gc.core_offset(), gc.width, gc.height,
-                                                                     u, g.pitch, g.core_offset(), g.width, g.height);
+  detail::mgp_prolong_add_kernel<T><<<grid, detail::kMgBlock, 0, s>>>(
+      e, gc.pitch, gc.core_offset(), gc.width, gc.height, u, g.pitch, g.core_offset(), g.width, g.height, sd);
   g_last_pcg = "mgp_prolong_add";
   MXS_HIP_CHECK_LAUNCH();
 }
 
 template <typename T>
-void mgp_coarse_solve(const T* src, T* e, const TileGeom& g, const MgSweepTable& t, int repeats, bool reflect_rows,
-                      bool reflect_cols, PcgScalars* scalars, hipStream_t s) {
+void mgp_coarse_solve(const T* src, T* e, const TileGeom& g, const MgSweepTable& t, int repeats, GhostSides sides,
+                      PcgScalars* scalars, hipStream_t s) {
   check_tile(g, "mgp_coarse_solve");
+  const detail::MgpSides sd = sides_of(sides, "mgp_coarse_solve");
   MXS_CHECK(reinterpret_cast<std::uintptr_t>(scalars) % sizeof(double) == 0, "mgp_coarse_solve: the scalar block must be aligned");
   MXS_CHECK(g.width <= kMgCoarsestMax && g.height <= kMgCoarsestMax,
             "mgp_coarse_solve: the grid must be at most " << kMgCoarsestMax << " on both sides, got " << g.width << " x "
@@ -150,19 +162,18 @@ void mgp_coarse_solve(const T* src, T* e, const TileGeom& g, const MgSweepTable&
   }
   detail::mgp_coarse_solve_kernel<T><<<1, detail::kMgBlock, lds, s>>>(src, e, g.pitch, g.core_offset(), int(g.width),
                                                                       int(g.height), repeats,
-                                                                      sweeps_of<T, kMaxLevels>(t), t.n,
-                                                                      int(reflect_rows), int(reflect_cols), scalars);
+                                                                      sweeps_of<T, kMaxLevels>(t), t.n, sd, scalars);
   g_last_pcg = "mgp_coarse_solve";
   MXS_HIP_CHECK_LAUNCH();
 }
 
 #define MXS_MGP_INSTANTIATE(T)                                                                                        \
-  template void mgp_smooth<T>(const T*, T*, const T*, const TileGeom&, const MgSweepTable&, bool, bool, PcgScalars*, \
+  template void mgp_smooth<T>(const T*, T*, const T*, const TileGeom&, const MgSweepTable&, GhostSides, PcgScalars*, \
                               double*, unsigned*, hipStream_t);                                                      \
-  template void mgp_residual_restrict<T>(const T*, const T*, const TileGeom&, bool, bool, T*, const TileGeom&,       \
+  template void mgp_residual_restrict<T>(const T*, const T*, const TileGeom&, GhostSides, T*, const TileGeom&,       \
                                          Stencil5Coeffs, hipStream_t);                                               \
-  template void mgp_prolong_add<T>(const T*, const TileGeom&, T*, const TileGeom&, hipStream_t);                      \
-  template void mgp_coarse_solve<T>(const T*, T*, const TileGeom&, const MgSweepTable&, int, bool, bool, PcgScalars*, \
+  template void mgp_prolong_add<T>(const T*, const TileGeom&, T*, const TileGeom&, hipStream_t, GhostSides);          \
+  template void mgp_coarse_solve<T>(const T*, T*, const TileGeom&, const MgSweepTable&, int, GhostSides, PcgScalars*, \
                                     hipStream_t);
 MXS_MGP_INSTANTIATE(float)
 MXS_MGP_INSTANTIATE(double)

@@ -4,6 +4,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <array>
 #include <sstream>
 
 #include "mxs/core/error.hpp"
@@ -329,6 +330,14 @@ PYBIND11_MODULE(_mxs_core, m) {
       "the coarsest level's solve: the 32-level Leja-ordered Chebyshev cycle as a sweep table, its error bound rho "
       "and the smallest repeat count with rho^repeats <= coarse_reduction");
   // Conjugate gradients (kernels/cg.hpp).
+  m.def(
+      "cg_check_sides",
+      [](double c0, double c1, const std::vector<std::string>& neumann) {
+        kernels::cg_check_sides(c0, c1, kernels::ghost_sides_of(neumann));
+      },
+      py::arg("c_center"), py::arg("c_neighbor"), py::arg("neumann") = std::vector<std::string>{},
+      "cg_check_operator, plus: unknown or repeated side names raise, and so do four Neumann sides with "
+      "c_center + 4 c_neighbor = 1 (the operator is then singular)");
   m.def("cg_check_operator", &kernels::cg_check_operator, py::arg("c_center"), py::arg("c_neighbor"),
         "raises ValueError unless c_neighbor > 0 and c_center + 4 c_neighbor <= 1 + 1e-12 (then (1 - c_center) v - "
         "c_neighbor (n + s + w + e) is symmetric positive definite)");
@@ -340,51 +349,54 @@ PYBIND11_MODULE(_mxs_core, m) {
     d["reflect_rows"] = l.reflect_rows;
     d["reflect_cols"] = l.reflect_cols;
     d["c_center"] = l.c0;
+    d["top"] = l.sides.top;
+    d["bottom"] = l.sides.bottom;
+    d["left"] = l.sides.left;
+    d["right"] = l.sides.right;
     return d;
   };
   m.def(
       "pcg_plan_levels",
-      [pcg_level_dict](long long w, long long h, double c0, double c1) {
+      [pcg_level_dict](long long w, long long h, double c0, double c1, const std::vector<std::string>& neumann) {
         py::list out;
-        for (const kernels::PcgLevel& l : kernels::pcg_plan_levels(w, h, c0, c1)) out.append(pcg_level_dict(l));
+        for (const kernels::PcgLevel& l : kernels::pcg_plan_levels(w, h, c0, c1, kernels::ghost_sides_of(neumann)))
+          out.append(pcg_level_dict(l));
         return out;
       },
       py::arg("width"), py::arg("height"), py::arg("c_center") = 0.2, py::arg("c_neighbor") = 0.2,
+      py::arg("neumann") = std::vector<std::string>{},
       "the preconditioner's levels of a width x height core, finest first, as dicts (width, height, reflect_rows, "
       "reflect_cols, c_center): n_c = floor(n / 2) on both axes while the larger side is above 31 and the smaller at "
       "least 2; a flag is set when the parent's height (rows) or width (cols) was even; raises ValueError when the "
       "coarsest level is above 63 on a side (the message names ConjugateGradient2D)");
-  auto pcg_level_of = [](long long w, long long h, bool rr, bool rc, double c0) {
-    kernels::PcgLevel l;
-    l.width = w;
-    l.height = h;
-    l.reflect_rows = rr;
-    l.reflect_cols = rc;
-    l.c0 = c0;
-    return l;
+  // `sides`: the four ghost codes (top, bottom, left, right); a set flag makes a far code of 0 a -1.
+  auto pcg_level_of = [](long long w, long long h, bool rr, bool rc, double c0, const std::array<int, 4>& sides) {
+    return kernels::pcg_level_of(w, h, rr, rc, c0, kernels::GhostSides{sides[0], sides[1], sides[2], sides[3]});
   };
+  const std::array<int, 4> no_sides{0, 0, 0, 0};
   m.def(
       "pcg_coarse_interval",
-      [pcg_level_of](long long w, long long h, bool rr, bool rc, double c0, double c1) {
-        const kernels::RelaxSpectrum sp = kernels::pcg_coarse_interval(pcg_level_of(w, h, rr, rc, c0), c1);
+      [pcg_level_of](long long w, long long h, bool rr, bool rc, double c0, double c1, const std::array<int, 4>& sides) {
+        const kernels::RelaxSpectrum sp = kernels::pcg_coarse_interval(pcg_level_of(w, h, rr, rc, c0, sides), c1);
         return std::make_pair(sp.a, sp.b);
       },
       py::arg("width"), py::arg("height"), py::arg("reflect_rows"), py::arg("reflect_cols"), py::arg("c_center"),
-      py::arg("c_neighbor"),
+      py::arg("c_neighbor"), py::arg("sides") = no_sides,
       "(a, b) the coarse solve of a level is built on: relaxation_spectrum's, with the Gershgorin upper end "
       "1 - c_center + 4 c_neighbor when a side reflects");
   m.def(
       "pcg_coarse_plan",
-      [sweep_dict, pcg_level_of](long long w, long long h, bool rr, bool rc, double c0, double c1, double reduction) {
-        const kernels::MgCoarsePlan p = kernels::pcg_coarse_plan(pcg_level_of(w, h, rr, rc, c0), c1, reduction);
+      [sweep_dict, pcg_level_of](long long w, long long h, bool rr, bool rc, double c0, double c1, double reduction,
+                                 const std::array<int, 4>& sides) {
+        const kernels::MgCoarsePlan p = kernels::pcg_coarse_plan(pcg_level_of(w, h, rr, rc, c0, sides), c1, reduction);
         py::dict d = sweep_dict(p.table);
         d["repeats"] = p.repeats;
         d["rho"] = p.rho;
         return d;
       },
       py::arg("width"), py::arg("height"), py::arg("reflect_rows"), py::arg("reflect_cols"), py::arg("c_center"),
-      py::arg("c_neighbor"), py::arg("coarse_reduction"),
-      "the coarsest level's solve: mg_coarse_plan without a reflecting side, else the 32-level cycle of pcg_coarse_interval");
+      py::arg("c_neighbor"), py::arg("coarse_reduction"), py::arg("sides") = no_sides,
+      "the coarsest level's solve: mg_coarse_plan without a reflecting or mirror side, else the 32-level cycle of pcg_coarse_interval");
   m.def(
       "chebyshev_cycle_interval",
       [](double a, double b, double c0, double c1, int M) {

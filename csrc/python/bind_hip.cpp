@@ -10,6 +10,7 @@
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
+#include <array>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -131,6 +132,15 @@ struct PcgHandle {
     return dt == DType::F32 ? fn(*f) : fn(*d);
   }
 };
+
+// Ghost codes (top, bottom, left, right) from Python; set reflect flags turn a far code of 0 into -1.
+kernels::GhostSides ghost_sides(const std::array<int, 4>& c, bool reflect_rows = false, bool reflect_cols = false) {
+  kernels::GhostSides sd{c[0], c[1], c[2], c[3]};
+  if (reflect_rows && sd.bottom == kernels::kGhostRing) sd.bottom = kernels::kGhostReflect;
+  if (reflect_cols && sd.right == kernels::kGhostRing) sd.right = kernels::kGhostReflect;
+  return sd;
+}
+const std::array<int, 4> kNoSides{0, 0, 0, 0};
 
 py::dict pcg_scalars_dict(const kernels::PcgScalars& s) {
   py::dict d;
@@ -1199,35 +1209,35 @@ PYBIND11_MODULE(_mxs_hip, m) {
       "cg_start",
       [](std::uintptr_t u, std::uintptr_t g, std::uintptr_t r, std::uintptr_t p, const TileGeom& geom, double c0,
          double c1, std::uintptr_t scalars, std::uintptr_t partials, std::uintptr_t counter, const std::string& dt,
-         std::uintptr_t s) {
+         std::uintptr_t s, const std::array<int, 4>& sides) {
         kernels::Stencil5Coeffs c{c0, c1, false, -1.0};
         if (parse_dtype(dt) == DType::F32)
           kernels::cg_start<float>(ptr<float>(u), ptr<float>(g), ptr<float>(r), ptr<float>(p), geom, c,
-                                   ptr<kernels::CgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+                                   ptr<kernels::CgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s), ghost_sides(sides));
         else
           kernels::cg_start<double>(ptr<double>(u), ptr<double>(g), ptr<double>(r), ptr<double>(p), geom, c,
-                                    ptr<kernels::CgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+                                    ptr<kernels::CgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s), ghost_sides(sides));
       },
       py::arg("u"), py::arg("g"), py::arg("r"), py::arg("p"), py::arg("geom"), py::arg("c_center"), py::arg("c_neighbor"),
-      py::arg("scalars"), py::arg("partials"), py::arg("counter"), py::arg("dtype") = "f64", py::arg("stream") = 0,
+      py::arg("scalars"), py::arg("partials"), py::arg("counter"), py::arg("dtype") = "f64", py::arg("stream") = 0, py::arg("sides") = kNoSides,
       "r = p = (fma(c1, (n + s) + (w + e), c0 v) + g) - v over the core; last workgroup: rr, linf, beta = 0, "
       "iteration = 0, status");
   m.def(
       "cg_apply",
       [](std::uintptr_t r, std::uintptr_t p_old, std::uintptr_t p_new, std::uintptr_t q, const TileGeom& geom, double c0,
          double c1, std::uintptr_t scalars, std::uintptr_t partials, std::uintptr_t counter, const std::string& dt,
-         std::uintptr_t s) {
+         std::uintptr_t s, const std::array<int, 4>& sides) {
         kernels::Stencil5Coeffs c{c0, c1, false, -1.0};
         if (parse_dtype(dt) == DType::F32)
           kernels::cg_apply<float>(ptr<float>(r), ptr<float>(p_old), ptr<float>(p_new), ptr<float>(q), geom, c,
-                                   ptr<kernels::CgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+                                   ptr<kernels::CgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s), ghost_sides(sides));
         else
           kernels::cg_apply<double>(ptr<double>(r), ptr<double>(p_old), ptr<double>(p_new), ptr<double>(q), geom, c,
-                                    ptr<kernels::CgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+                                    ptr<kernels::CgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s), ghost_sides(sides));
       },
       py::arg("r"), py::arg("p_old"), py::arg("p_new"), py::arg("q"), py::arg("geom"), py::arg("c_center"),
       py::arg("c_neighbor"), py::arg("scalars"), py::arg("partials"), py::arg("counter"), py::arg("dtype") = "f64",
-      py::arg("stream") = 0,
+      py::arg("stream") = 0, py::arg("sides") = kNoSides,
       "p_new = fma(T(beta), p_old, r), q = fma(-c1, (n + s) + (w + e), T(1 - c0) p_new) with p_new = 0 outside the "
       "core; last workgroup: pq, alpha (or status 3)");
   m.def(
@@ -1248,8 +1258,10 @@ PYBIND11_MODULE(_mxs_hip, m) {
         "the kernel the most recent CG launcher ran ('' before the first)");
 
   py::class_<CgHandle>(m, "CgSolver")
-      .def(py::init([](index_t w, index_t h, const std::string& dt, double c0, double c1, bool graph) {
+      .def(py::init([](index_t w, index_t h, const std::string& dt, double c0, double c1, bool graph,
+                       const std::vector<std::string>& neumann) {
              CgConfig cfg;
+             cfg.neumann = neumann;
              cfg.width = w;
              cfg.height = h;
              cfg.c_center = c0;
@@ -1262,7 +1274,7 @@ PYBIND11_MODULE(_mxs_hip, m) {
              return h_;
            }),
            py::arg("width"), py::arg("height"), py::arg("dtype") = "f64", py::arg("c_center") = 0.2,
-           py::arg("c_neighbor") = 0.2, py::arg("graph") = true)
+           py::arg("c_neighbor") = 0.2, py::arg("graph") = true, py::arg("neumann") = std::vector<std::string>{})
       .def("geom", [](CgHandle& h) { return h.visit([](auto& s) { return s.geom(); }); })
       .def(
           "set_boundary",
@@ -1348,35 +1360,35 @@ PYBIND11_MODULE(_mxs_hip, m) {
   m.def(
       "pcg_start",
       [](std::uintptr_t u, std::uintptr_t g, std::uintptr_t r, const TileGeom& geom, double c0, double c1,
-         std::uintptr_t scalars, std::uintptr_t partials, std::uintptr_t counter, const std::string& dt, std::uintptr_t s) {
+         std::uintptr_t scalars, std::uintptr_t partials, std::uintptr_t counter, const std::string& dt, std::uintptr_t s, const std::array<int, 4>& sides) {
         kernels::Stencil5Coeffs c{c0, c1, false, -1.0};
         if (parse_dtype(dt) == DType::F32)
           kernels::pcg_start<float>(ptr<float>(u), ptr<float>(g), ptr<float>(r), geom, c,
-                                    ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+                                    ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s), ghost_sides(sides));
         else
           kernels::pcg_start<double>(ptr<double>(u), ptr<double>(g), ptr<double>(r), geom, c,
-                                     ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+                                     ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s), ghost_sides(sides));
       },
       py::arg("u"), py::arg("g"), py::arg("r"), py::arg("geom"), py::arg("c_center"), py::arg("c_neighbor"),
-      py::arg("scalars"), py::arg("partials"), py::arg("counter"), py::arg("dtype") = "f64", py::arg("stream") = 0,
+      py::arg("scalars"), py::arg("partials"), py::arg("counter"), py::arg("dtype") = "f64", py::arg("stream") = 0, py::arg("sides") = kNoSides,
       "r = (fma(c1, (n + s) + (w + e), c0 v) + g) - v over the core; last workgroup: rr, linf, rz = beta = 0, "
       "iteration = 0, status");
   m.def(
       "pcg_apply",
       [](std::uintptr_t z, std::uintptr_t p_old, std::uintptr_t p_new, std::uintptr_t q, const TileGeom& geom, double c0,
          double c1, std::uintptr_t scalars, std::uintptr_t partials, std::uintptr_t counter, const std::string& dt,
-         std::uintptr_t s) {
+         std::uintptr_t s, const std::array<int, 4>& sides) {
         kernels::Stencil5Coeffs c{c0, c1, false, -1.0};
         if (parse_dtype(dt) == DType::F32)
           kernels::pcg_apply<float>(ptr<float>(z), ptr<float>(p_old), ptr<float>(p_new), ptr<float>(q), geom, c,
-                                    ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+                                    ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s), ghost_sides(sides));
         else
           kernels::pcg_apply<double>(ptr<double>(z), ptr<double>(p_old), ptr<double>(p_new), ptr<double>(q), geom, c,
-                                     ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
+                                     ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s), ghost_sides(sides));
       },
       py::arg("z"), py::arg("p_old"), py::arg("p_new"), py::arg("q"), py::arg("geom"), py::arg("c_center"),
       py::arg("c_neighbor"), py::arg("scalars"), py::arg("partials"), py::arg("counter"), py::arg("dtype") = "f64",
-      py::arg("stream") = 0,
+      py::arg("stream") = 0, py::arg("sides") = kNoSides,
       "p_new = fma(T(beta), p_old, z), q = L p_new; last workgroup: pq, alpha = rz / pq (or status 3)");
   m.def(
       "pcg_update",
@@ -1397,68 +1409,72 @@ PYBIND11_MODULE(_mxs_hip, m) {
       [sweep_table](std::uintptr_t in, std::uintptr_t out, std::uintptr_t src, const TileGeom& g,
                     const std::vector<double>& center, const std::vector<double>& neighbor,
                     const std::vector<double>& weight, bool rr, bool rc, std::uintptr_t scalars, std::uintptr_t partials,
-                    std::uintptr_t counter, const std::string& dt, std::uintptr_t s) {
+                    std::uintptr_t counter, const std::string& dt, std::uintptr_t s, const std::array<int, 4>& sides) {
+        const kernels::GhostSides sd = ghost_sides(sides, rr, rc);
         const kernels::MgSweepTable t = sweep_table(center, neighbor, weight);
         if (parse_dtype(dt) == DType::F32)
-          kernels::mgp_smooth<float>(ptr<float>(in), ptr<float>(out), ptr<float>(src), g, t, rr, rc,
+          kernels::mgp_smooth<float>(ptr<float>(in), ptr<float>(out), ptr<float>(src), g, t, sd,
                                      ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
         else
-          kernels::mgp_smooth<double>(ptr<double>(in), ptr<double>(out), ptr<double>(src), g, t, rr, rc,
+          kernels::mgp_smooth<double>(ptr<double>(in), ptr<double>(out), ptr<double>(src), g, t, sd,
                                       ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s));
       },
       py::arg("u_in"), py::arg("u_out"), py::arg("src"), py::arg("geom"), py::arg("center"), py::arg("neighbor"),
       py::arg("weight"), py::arg("reflect_rows") = false, py::arg("reflect_cols") = false, py::arg("scalars") = 0,
-      py::arg("partials") = 0, py::arg("counter") = 0, py::arg("dtype") = "f32", py::arg("stream") = 0,
+      py::arg("partials") = 0, py::arg("counter") = 0, py::arg("dtype") = "f32", py::arg("stream") = 0, py::arg("sides") = kNoSides,
       "mg_smooth with reflecting ghosts; with scalars, partials and counter also the dot epilogue (rz, beta)");
   m.def(
       "mgp_residual_restrict",
       [](std::uintptr_t u, std::uintptr_t src, const TileGeom& g, bool rr, bool rc, std::uintptr_t csrc, const TileGeom& gc,
-         double c0, double c1, const std::string& dt, std::uintptr_t s) {
+         double c0, double c1, const std::string& dt, std::uintptr_t s, const std::array<int, 4>& sides) {
+        const kernels::GhostSides sd = ghost_sides(sides, rr, rc);
         kernels::Stencil5Coeffs c{c0, c1, false, -1.0};
         if (parse_dtype(dt) == DType::F32)
-          kernels::mgp_residual_restrict<float>(ptr<float>(u), ptr<float>(src), g, rr, rc, ptr<float>(csrc), gc, c, strm(s));
+          kernels::mgp_residual_restrict<float>(ptr<float>(u), ptr<float>(src), g, sd, ptr<float>(csrc), gc, c, strm(s));
         else
-          kernels::mgp_residual_restrict<double>(ptr<double>(u), ptr<double>(src), g, rr, rc, ptr<double>(csrc), gc, c,
+          kernels::mgp_residual_restrict<double>(ptr<double>(u), ptr<double>(src), g, sd, ptr<double>(csrc), gc, c,
                                                  strm(s));
       },
       py::arg("u"), py::arg("src"), py::arg("geom"), py::arg("reflect_rows"), py::arg("reflect_cols"),
       py::arg("coarse_src"), py::arg("coarse_geom"), py::arg("c_center") = 0.2, py::arg("c_neighbor") = 0.2,
-      py::arg("dtype") = "f32", py::arg("stream") = 0,
+      py::arg("dtype") = "f32", py::arg("stream") = 0, py::arg("sides") = kNoSides,
       "coarse_src core = 4 R ((A u + src) - u) for a coarse tile of (width / 2) x (height / 2), fine residuals outside "
       "the core 0, the fine level's reflecting ghost read");
   m.def(
       "mgp_prolong_add",
       [](std::uintptr_t e, const TileGeom& gc, std::uintptr_t u, const TileGeom& g, const std::string& dt,
-         std::uintptr_t s) {
-        if (parse_dtype(dt) == DType::F32) kernels::mgp_prolong_add<float>(ptr<float>(e), gc, ptr<float>(u), g, strm(s));
-        else kernels::mgp_prolong_add<double>(ptr<double>(e), gc, ptr<double>(u), g, strm(s));
+         std::uintptr_t s, const std::array<int, 4>& sides) {
+        if (parse_dtype(dt) == DType::F32) kernels::mgp_prolong_add<float>(ptr<float>(e), gc, ptr<float>(u), g, strm(s), ghost_sides(sides));
+        else kernels::mgp_prolong_add<double>(ptr<double>(e), gc, ptr<double>(u), g, strm(s), ghost_sides(sides));
       },
       py::arg("e"), py::arg("coarse_geom"), py::arg("u"), py::arg("geom"), py::arg("dtype") = "f32",
-      py::arg("stream") = 0, "u core += P e for a coarse tile of (width / 2) x (height / 2)");
+      py::arg("stream") = 0, py::arg("sides") = kNoSides, "u core += P e for a coarse tile of (width / 2) x (height / 2)");
   m.def(
       "mgp_coarse_solve",
       [sweep_table](std::uintptr_t src, std::uintptr_t e, const TileGeom& g, const std::vector<double>& center,
                     const std::vector<double>& neighbor, const std::vector<double>& weight, int repeats, bool rr, bool rc,
-                    std::uintptr_t scalars, const std::string& dt, std::uintptr_t s) {
+                    std::uintptr_t scalars, const std::string& dt, std::uintptr_t s, const std::array<int, 4>& sides) {
+        const kernels::GhostSides sd = ghost_sides(sides, rr, rc);
         const kernels::MgSweepTable t = sweep_table(center, neighbor, weight);
         if (parse_dtype(dt) == DType::F32)
-          kernels::mgp_coarse_solve<float>(ptr<float>(src), ptr<float>(e), g, t, repeats, rr, rc,
+          kernels::mgp_coarse_solve<float>(ptr<float>(src), ptr<float>(e), g, t, repeats, sd,
                                            ptr<kernels::PcgScalars>(scalars), strm(s));
         else
-          kernels::mgp_coarse_solve<double>(ptr<double>(src), ptr<double>(e), g, t, repeats, rr, rc,
+          kernels::mgp_coarse_solve<double>(ptr<double>(src), ptr<double>(e), g, t, repeats, sd,
                                             ptr<kernels::PcgScalars>(scalars), strm(s));
       },
       py::arg("src"), py::arg("e"), py::arg("geom"), py::arg("center"), py::arg("neighbor"), py::arg("weight"),
       py::arg("repeats"), py::arg("reflect_rows") = false, py::arg("reflect_cols") = false, py::arg("scalars") = 0,
-      py::arg("dtype") = "f32", py::arg("stream") = 0,
+      py::arg("dtype") = "f32", py::arg("stream") = 0, py::arg("sides") = kNoSides,
       "mg_coarse_solve with reflecting ghosts; with scalars also the dot epilogue of a single-level preconditioner");
   m.def("last_pcg_dispatch", [] { return std::string(kernels::last_pcg_dispatch()); },
         "the kernel the most recent preconditioner launcher ran ('' before the first)");
 
   py::class_<PcgHandle>(m, "PcgSolver")
       .def(py::init([](index_t w, index_t h, const std::string& dt, double c0, double c1, int nu, double omega,
-                       double coarse_reduction, bool graph) {
+                       double coarse_reduction, bool graph, const std::vector<std::string>& neumann) {
              PcgConfig cfg;
+             cfg.neumann = neumann;
              cfg.width = w;
              cfg.height = h;
              cfg.c_center = c0;
@@ -1475,14 +1491,15 @@ PYBIND11_MODULE(_mxs_hip, m) {
            }),
            py::arg("width"), py::arg("height"), py::arg("dtype") = "f64", py::arg("c_center") = 0.2,
            py::arg("c_neighbor") = 0.2, py::arg("nu") = 2, py::arg("smoother_omega") = 0.8,
-           py::arg("coarse_reduction") = 1e-3, py::arg("graph") = true)
+           py::arg("coarse_reduction") = 1e-3, py::arg("graph") = true,
+           py::arg("neumann") = std::vector<std::string>{})
       .def("geom", [](PcgHandle& h) { return h.visit([](auto& s) { return s.geom(); }); })
       .def("levels",
            [](PcgHandle& h) {
              py::list out;
              h.visit([&](auto& s) {
                for (const auto& l : s.levels())
-                 out.append(py::make_tuple(l.width, l.height, l.reflect_rows, l.reflect_cols, l.c0));
+                 out.append(py::make_tuple(l.width, l.height, l.reflect_rows, l.reflect_cols, l.c0));  // codes: pcg_plan_levels
              });
              return out;
            })

@@ -8,8 +8,8 @@
 namespace mxs {
 
 template <typename T>
-CgSolver<T>::CgSolver(const CgConfig& cfg) : cfg_(cfg) {
-  kernels::cg_check_operator(cfg.c_center, cfg.c_neighbor);
+CgSolver<T>::CgSolver(const CgConfig& cfg) : cfg_(cfg), sides_(kernels::ghost_sides_of(cfg.neumann)) {
+  kernels::cg_check_sides(cfg.c_center, cfg.c_neighbor, sides_);
   if (cfg.width < 1 || cfg.height < 1) throw std::invalid_argument("conjugate gradients: the grid must be non-empty");
   geom_ = TileGeom::aligned(cfg.width, cfg.height, 1, 1, int(sizeof(T)));
   for (DeviceBuffer<T>* b : {&u_, &g_, &r_, &q_, &p_[0], &p_[1]}) {
@@ -18,6 +18,8 @@ CgSolver<T>::CgSolver(const CgConfig& cfg) : cfg_(cfg) {
   }
   scalars_.reset(1);
   MXS_HIP_CHECK(hipMemsetAsync(scalars_.get(), 0, sizeof(kernels::CgScalars), stream_.get()));
+  residual_scalars_.reset(1);
+  MXS_HIP_CHECK(hipMemsetAsync(residual_scalars_.get(), 0, sizeof(kernels::CgScalars), stream_.get()));
   partials_.reset(2 * index_t(kernels::cg_grid_size(geom_)));
   counter_.reset(1);
   MXS_HIP_CHECK(hipMemsetAsync(counter_.get(), 0, sizeof(unsigned), stream_.get()));
@@ -73,6 +75,18 @@ template <typename T>
 CgResidual CgSolver<T>::residual() {
   auto* norms = reinterpret_cast<kernels::ResidualNorms*>(residual_buf_.get());
   kernels::Stencil5Coeffs c{cfg_.c_center, cfg_.c_neighbor, false, -1.0};
+  if (sides_.any_mirror()) {  // stencil5_residual knows only the ring: cg_start computes exactly this residual
+    kernels::cg_start<T>(u_.get(), g_.get(), q_.get(), p_[1].get(), geom_, c, residual_scalars_.get(), partials_.get(),
+                         counter_.get(), stream_.get(), sides_);
+    MXS_HIP_CHECK(hipMemcpyAsync(scalars_host_.get() + 1, residual_scalars_.get(), sizeof(kernels::CgScalars),
+                                 hipMemcpyDeviceToHost, stream_.get()));
+    stream_.spin_sync();
+    CgResidual r;
+    r.linf = scalars_host_.get()[1].linf;
+    r.l2 = std::sqrt(scalars_host_.get()[1].rr);
+    r.cells = geom_.width * geom_.height;
+    return r;
+  }
   kernels::stencil5_residual<T>(u_.get(), geom_, c, norms, residual_buf_.get() + 2, residual_counter_.get(),
                                 stream_.get(), g_.get());
   MXS_HIP_CHECK(hipMemcpyAsync(residual_host_.get(), norms, sizeof(kernels::ResidualNorms), hipMemcpyDeviceToHost,
@@ -110,7 +124,7 @@ kernels::CgScalars CgSolver<T>::start(double tol, int max_iters, int norm) {
   MXS_HIP_CHECK(hipMemsetAsync(counter_.get(), 0, sizeof(unsigned), s));
   const kernels::Stencil5Coeffs c{cfg_.c_center, cfg_.c_neighbor, false, -1.0};
   kernels::cg_start<T>(u_.get(), g_.get(), r_.get(), p_[0].get(), geom_, c, scalars_.get(), partials_.get(),
-                       counter_.get(), s);
+                       counter_.get(), s, sides_);
   return read_scalars();
 }
 
@@ -122,7 +136,7 @@ void CgSolver<T>::enqueue_iterations(int n, int parity) {
   for (int i = 0; i < n; ++i) {
     const int a = (parity + i) & 1;
     kernels::cg_apply<T>(r_.get(), p_[a].get(), p_[a ^ 1].get(), q_.get(), geom_, c, scalars_.get(), partials_.get(),
-                         counter_.get(), s);
+                         counter_.get(), s, sides_);
     kernels::cg_update<T>(u_.get(), r_.get(), p_[a ^ 1].get(), q_.get(), geom_, scalars_.get(), partials_.get(),
                           counter_.get(), s);
   }
@@ -228,7 +242,8 @@ template <typename T>
 std::string CgSolver<T>::note() const {
   std::ostringstream os;
   os << "conjugate gradients " << cfg_.width << "x" << cfg_.height << ", c_center " << cfg_.c_center << ", c_neighbor "
-     << cfg_.c_neighbor << ", 2 kernels per iteration (cg_apply, cg_update) on " << kernels::cg_grid_size(geom_)
+     << cfg_.c_neighbor << (sides_.any_mirror() ? ", Neumann sides " + kernels::ghost_sides_names(sides_) : std::string())
+     << ", 2 kernels per iteration (cg_apply, cg_update) on " << kernels::cg_grid_size(geom_)
      << " workgroups at most, graph " << graph_status_;
   if (graph_.valid()) os << " (" << graph_iters_ << " iterations per launch)";
   return os.str();

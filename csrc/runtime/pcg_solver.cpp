@@ -9,8 +9,8 @@
 namespace mxs {
 
 template <typename T>
-PcgSolver<T>::PcgSolver(const PcgConfig& cfg) : cfg_(cfg) {
-  plan_ = kernels::pcg_plan_levels(cfg.width, cfg.height, cfg.c_center, cfg.c_neighbor);
+PcgSolver<T>::PcgSolver(const PcgConfig& cfg) : cfg_(cfg), sides_(kernels::ghost_sides_of(cfg.neumann)) {
+  plan_ = kernels::pcg_plan_levels(cfg.width, cfg.height, cfg.c_center, cfg.c_neighbor, sides_);
   coarse_ = kernels::pcg_coarse_plan(plan_.back(), cfg.c_neighbor, cfg.coarse_reduction);
   geom_ = TileGeom::aligned(cfg.width, cfg.height, 1, 1, int(sizeof(T)));
   for (DeviceBuffer<T>* b : {&u_, &g_, &r_, &q_, &p_[0], &p_[1]}) {
@@ -30,6 +30,8 @@ PcgSolver<T>::PcgSolver(const PcgConfig& cfg) : cfg_(cfg) {
   }
   scalars_.reset(1);
   MXS_HIP_CHECK(hipMemsetAsync(scalars_.get(), 0, sizeof(kernels::PcgScalars), stream_.get()));
+  residual_scalars_.reset(1);
+  MXS_HIP_CHECK(hipMemsetAsync(residual_scalars_.get(), 0, sizeof(kernels::PcgScalars), stream_.get()));
   partials_.reset(2 * index_t(std::max(kernels::cg_grid_size(geom_), kernels::mgp_smooth_grid_size(geom_))));
   counter_.reset(1);
   MXS_HIP_CHECK(hipMemsetAsync(counter_.get(), 0, sizeof(unsigned), stream_.get()));
@@ -41,7 +43,7 @@ PcgSolver<T>::PcgSolver(const PcgConfig& cfg) : cfg_(cfg) {
   // first use); a source of 0 gives e = 0.
   Level& c = lv_.back();
   kernels::mgp_coarse_solve<T>(lv_.size() == 1 ? r_.get() : c.g.get(), c.u[0].get(), c.geom, coarse_.table, 1,
-                               plan_.back().reflect_rows, plan_.back().reflect_cols, nullptr, stream_.get());
+                               plan_.back().sides, nullptr, stream_.get());
   stream_.sync();
 }
 
@@ -90,6 +92,18 @@ template <typename T>
 CgResidual PcgSolver<T>::residual() {
   auto* norms = reinterpret_cast<kernels::ResidualNorms*>(residual_buf_.get());
   kernels::Stencil5Coeffs c{cfg_.c_center, cfg_.c_neighbor, false, -1.0};
+  if (sides_.any_mirror()) {  // CgSolver::residual: pcg_start's residual into the scratch tile q
+    kernels::pcg_start<T>(u_.get(), g_.get(), q_.get(), geom_, c, residual_scalars_.get(), partials_.get(),
+                          counter_.get(), stream_.get(), sides_);
+    MXS_HIP_CHECK(hipMemcpyAsync(scalars_host_.get() + 1, residual_scalars_.get(), sizeof(kernels::PcgScalars),
+                                 hipMemcpyDeviceToHost, stream_.get()));
+    stream_.spin_sync();
+    CgResidual r;
+    r.linf = scalars_host_.get()[1].linf;
+    r.l2 = std::sqrt(scalars_host_.get()[1].rr);
+    r.cells = geom_.width * geom_.height;
+    return r;
+  }
   kernels::stencil5_residual<T>(u_.get(), geom_, c, norms, residual_buf_.get() + 2, residual_counter_.get(),
                                 stream_.get(), g_.get());
   MXS_HIP_CHECK(hipMemcpyAsync(residual_host_.get(), norms, sizeof(kernels::ResidualNorms), hipMemcpyDeviceToHost,
@@ -128,7 +142,8 @@ kernels::PcgScalars PcgSolver<T>::start(double tol, int max_iters, int norm) {
   // The first direction is fma(0, p_old, z): p_old has to be finite.
   MXS_HIP_CHECK(hipMemsetAsync(p_[0].get(), 0, p_[0].bytes(), s));
   const kernels::Stencil5Coeffs c{cfg_.c_center, cfg_.c_neighbor, false, -1.0};
-  kernels::pcg_start<T>(u_.get(), g_.get(), r_.get(), geom_, c, scalars_.get(), partials_.get(), counter_.get(), s);
+  kernels::pcg_start<T>(u_.get(), g_.get(), r_.get(), geom_, c, scalars_.get(), partials_.get(), counter_.get(), s,
+                        sides_);
   return read_scalars();
 }
 
@@ -145,21 +160,20 @@ void PcgSolver<T>::enqueue_level(size_t k) {
   const T* src = k == 0 ? r_.get() : l.g.get();
   kernels::PcgScalars* dot = k == 0 ? scalars_.get() : nullptr;
   if (k + 1 == lv_.size()) {
-    kernels::mgp_coarse_solve<T>(src, l.u[0].get(), l.geom, coarse_.table, coarse_.repeats, pl.reflect_rows,
-                                 pl.reflect_cols, dot, s);
+    kernels::mgp_coarse_solve<T>(src, l.u[0].get(), l.geom, coarse_.table, coarse_.repeats, pl.sides, dot, s);
     ++launches_;
     return;
   }
   Level& c = lv_[k + 1];
   const kernels::Stencil5Coeffs co{pl.c0, cfg_.c_neighbor, false, -1.0};
   // Every level starts from e = 0: the pre-smooth takes it as given, no tile is zeroed or read.
-  kernels::mgp_smooth<T>(static_cast<const T*>(nullptr), l.u[1].get(), src, l.geom, l.smooth, pl.reflect_rows,
-                         pl.reflect_cols, nullptr, nullptr, nullptr, s);
-  kernels::mgp_residual_restrict<T>(l.u[1].get(), src, l.geom, pl.reflect_rows, pl.reflect_cols, c.g.get(), c.geom, co, s);
+  kernels::mgp_smooth<T>(static_cast<const T*>(nullptr), l.u[1].get(), src, l.geom, l.smooth, pl.sides, nullptr, nullptr,
+                         nullptr, s);
+  kernels::mgp_residual_restrict<T>(l.u[1].get(), src, l.geom, pl.sides, c.g.get(), c.geom, co, s);
   launches_ += 2;
   enqueue_level(k + 1);
-  kernels::mgp_prolong_add<T>(c.u[0].get(), c.geom, l.u[1].get(), l.geom, s);
-  kernels::mgp_smooth<T>(l.u[1].get(), l.u[0].get(), src, l.geom, l.smooth, pl.reflect_rows, pl.reflect_cols, dot,
+  kernels::mgp_prolong_add<T>(c.u[0].get(), c.geom, l.u[1].get(), l.geom, s, pl.sides);
+  kernels::mgp_smooth<T>(l.u[1].get(), l.u[0].get(), src, l.geom, l.smooth, pl.sides, dot,
                          dot ? partials_.get() : nullptr, dot ? counter_.get() : nullptr, s);
   launches_ += 2;
 }
@@ -175,7 +189,7 @@ void PcgSolver<T>::enqueue_iterations(int n, int parity) {
     launches_ = 0;
     enqueue_level(0);
     kernels::pcg_apply<T>(z, p_[a].get(), p_[a ^ 1].get(), q_.get(), geom_, c, scalars_.get(), partials_.get(),
-                          counter_.get(), s);
+                          counter_.get(), s, sides_);
     kernels::pcg_update<T>(u_.get(), r_.get(), p_[a ^ 1].get(), q_.get(), geom_, scalars_.get(), partials_.get(),
                            counter_.get(), s);
     launches_ += 2;
@@ -282,7 +296,8 @@ template <typename T>
 std::string PcgSolver<T>::note() const {
   std::ostringstream os;
   os << "multigrid-preconditioned CG " << cfg_.width << "x" << cfg_.height << ", c_center " << cfg_.c_center
-     << ", c_neighbor " << cfg_.c_neighbor << ", V(" << cfg_.nu << "," << cfg_.nu << ") over " << plan_.size()
+     << ", c_neighbor " << cfg_.c_neighbor
+     << (sides_.any_mirror() ? ", Neumann sides " + kernels::ghost_sides_names(sides_) : std::string()) << ", V(" << cfg_.nu << "," << cfg_.nu << ") over " << plan_.size()
      << " levels down to " << plan_.back().width << "x" << plan_.back().height << ", smoother omega "
      << cfg_.smoother_omega << ", coarse solve " << coarse_.repeats << " x " << coarse_.table.n
      << " Chebyshev sweeps (rho " << coarse_.rho << "), graph " << graph_status_;

@@ -8,7 +8,10 @@ gradients"). On a GPU ``ConjugateGradient2D`` drives the native ``CgSolver`` (tw
 HIP kernels per iteration with every dot product fused in, a captured hipGraph
 per ``check_every`` iterations, the stopping test on the device); on the CPU it
 runs the pure-torch references of ``ops.cg``, the same operations in the same
-order. One process only: a decomposed grid would need a halo exchange of the
+order. ``CgConfig(neumann=("left", "right"))`` makes those sides Neumann (insulated
+walls, symmetry planes, prescribed fluxes): the ring there holds the outward
+difference ``d = u_ghost - u_edge`` (``h du/dn``; 0 by default) instead of a value
+(docs/ARCHITECTURE.md "Neumann sides"). One process only: a decomposed grid would need a halo exchange of the
 direction and an all-reduce of the scalars.
 
 Which solver when: ``Multigrid2D`` where it applies (sides ``m 2^k - 1``, pure
@@ -45,15 +48,17 @@ class CgConfig:
     c_neighbor: float = 0.2
     graph: bool = True
     check_every: int = 32
+    neumann: tuple = ()  # the Neumann sides, any of "top", "bottom", "left", "right"; the others are Dirichlet
 
     def __post_init__(self):
+        self.neumann = cg.neumann_sides(self.neumann)
         if self.dtype not in _DTYPES:
             raise ValueError(f"dtype must be f32 or f64, got {self.dtype!r}")
         if self.width < 1 or self.height < 1:
             raise ValueError("conjugate gradients: the grid must be non-empty")
         if self.check_every < 1:
             raise ValueError(f"conjugate gradients: check_every must be >= 1, got {self.check_every}")
-        core().cg_check_operator(float(self.c_center), float(self.c_neighbor))
+        cg.cg_check_sides(self.c_center, self.c_neighbor, self.neumann)
 
 
 class ConjugateGradient2D:
@@ -69,7 +74,8 @@ class ConjugateGradient2D:
         self.iterations_run = 0
         if self.device.type == "cuda":
             with torch.cuda.device(self.device):
-                self.solver = hip().CgSolver(cfg.width, cfg.height, cfg.dtype, cfg.c_center, cfg.c_neighbor, cfg.graph)
+                self.solver = hip().CgSolver(cfg.width, cfg.height, cfg.dtype, cfg.c_center, cfg.c_neighbor, cfg.graph,
+                                             list(cfg.neumann))
             self.geom = self.solver.geom()
         else:
             self.solver = None
@@ -89,7 +95,8 @@ class ConjugateGradient2D:
     def set_boundary(self, top=None, bottom=None, left=None, right=None):
         """Dirichlet values of the ring: each argument is a scalar or a 1-D tensor
         over the width (top, bottom) or height (left, right); None leaves that side
-        as it is (the ring starts at 0)."""
+        as it is (the ring starts at 0). On a Neumann side the values are the
+        prescribed outward differences ``d = u_ghost - u_edge`` (0: insulated)."""
         def values(v, n, what):
             if v is None:
                 return None
@@ -175,11 +182,14 @@ class ConjugateGradient2D:
     # ---------------------------------------------------------------- solving
     def residual(self) -> dict:
         """``{"linf", "l2", "cells"}`` of the true residual ``r = (A u + g) - u`` over the
-        core: the HIP kernel ``stencil5_residual`` with the source, or its CPU reference."""
+        core: the HIP kernel ``stencil5_residual`` with the source, or its CPU reference.
+        With a Neumann side the ghost there is ``edge + ring`` on both devices (on the
+        GPU the start kernel's residual; not to be called while a solve runs)."""
         if self.solver is not None:
             r = self.solver.residual()
             return {"linf": float(r["linf"]), "l2": float(r["l2"]), "cells": int(r["cells"])}
-        linf, l2 = ops.residual5_reference(self._full, 1, self.cfg.c_center, self.cfg.c_neighbor, source=self._g)
+        linf, l2 = ops.residual5_reference(cg.ghosted(self._full, self.cfg.neumann), 1, self.cfg.c_center,
+                                           self.cfg.c_neighbor, source=self._g)
         return {"linf": linf, "l2": l2, "cells": self.cfg.width * self.cfg.height}
 
     def solve(self, tol: float, max_iters: int = 10000, norm: str = "l2", check_every: int | None = None) -> dict:
@@ -204,7 +214,8 @@ class ConjugateGradient2D:
             out = dict(self.solver.solve(float(tol), int(max_iters), norm, every))
             out["history"] = [tuple(h) for h in out["history"]]
         else:
-            out = cg.cg_reference(self._full, self._g, c.c_center, c.c_neighbor, float(tol), int(max_iters), norm)
+            out = cg.cg_reference(self._full, self._g, c.c_center, c.c_neighbor, float(tol), int(max_iters), norm,
+                                  neumann=c.neumann)
             self._full = out.pop("full")
         self.iterations_run += out["iterations"]
         return out
@@ -224,7 +235,8 @@ class ConjugateGradient2D:
         if self.solver is not None:
             return self.solver.note()
         c = self.cfg
-        return (f"conjugate gradients {c.width}x{c.height}, c_center {c.c_center:g}, c_neighbor {c.c_neighbor:g}, "
+        sides = f", Neumann sides {', '.join(c.neumann)}" if c.neumann else ""
+        return (f"conjugate gradients {c.width}x{c.height}, c_center {c.c_center:g}, c_neighbor {c.c_neighbor:g}{sides}, "
                 "torch references")
 
 
@@ -245,15 +257,18 @@ def main(argv=None) -> int:
     p.add_argument("--c-center", type=float, default=0.2)
     p.add_argument("--c-neighbor", type=float, default=0.2)
     p.add_argument("--check-every", type=int, default=32)
+    p.add_argument("--neumann", default="", metavar="SIDES",
+                   help="comma-separated Neumann (insulated) sides out of top,bottom,left,right; the others are Dirichlet")
     p.add_argument("--no-graph", action="store_true")
     p.add_argument("--device", default=None)
     p.add_argument("--json", default=None)
     args = p.parse_args(argv)
     w, h = _parse_wh(args.size)
     cfg = CgConfig(width=w, height=h, dtype=args.dtype, c_center=args.c_center, c_neighbor=args.c_neighbor,
-                   graph=not args.no_graph, check_every=args.check_every)
+                   graph=not args.no_graph, check_every=args.check_every, neumann=cg.neumann_sides(args.neumann))
     m = ConjugateGradient2D(cfg, device=args.device)
-    m.set_boundary(top=args.boundary)
+    if "top" not in cfg.neumann:  # a Neumann top stays insulated
+        m.set_boundary(top=args.boundary)
     m.set_source(args.source)
     if m.solver is not None:  # capture and warm up outside the timed region, then restore the start
         m.solve(args.tol, min(args.max_iters, 2 * args.check_every), args.norm)
@@ -263,7 +278,8 @@ def main(argv=None) -> int:
     out = m.solve(args.tol, args.max_iters, args.norm)
     dt = time.perf_counter() - t0
     rec = {"metric": "cg2d_solve_s", "value": dt, "config": asdict(cfg), "device": str(m.device), "note": m.note(),
-           "graph": m.graph_status(), "source": args.source, "boundary": args.boundary, "tol": args.tol,
+           "graph": m.graph_status(), "source": args.source, "boundary": args.boundary,
+           "neumann": list(cfg.neumann), "tol": args.tol,
            "norm": out["norm"], "converged": out["converged"], "iterations": out["iterations"],
            "residual": out["residual"], "reason": out["reason"], "restarts": out["restarts"],
            "history": out["history"][-8:]}

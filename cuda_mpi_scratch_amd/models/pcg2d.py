@@ -11,12 +11,16 @@ where plain CG needs thousands. On a GPU ``MultigridPcg2D`` drives the native
 ``PcgSolver`` (HIP kernels, the dot products fused in, a linear captured hipGraph
 per ``check_every`` iterations, the stopping test on the device); on the CPU it
 runs the pure-torch references of ``ops.pcg``, the same operations in the same
-order. One process only.
+order. ``PcgConfig(neumann=("left", "right"))`` makes those sides Neumann
+(``ConjugateGradient2D``'s rule: the ring there holds the outward difference, 0 for
+an insulated wall); every level of the preconditioner then mirrors at them,
+transfers included, and the iteration count stays where the all-Dirichlet one is
+(docs/ARCHITECTURE.md "Neumann sides"). One process only.
 
 Which solver when: ``MultigridPcg2D`` for a single-process Poisson or screened
-solve of any size; ``Multigrid2D`` where it applies (sides ``m 2^k - 1``, pure
+solve of any size, with Dirichlet or Neumann sides; ``Multigrid2D`` where it applies (sides ``m 2^k - 1``, pure
 Laplace weights) and a stand-alone cycle is wanted; ``ConjugateGradient2D`` for
-very thin grids; Chebyshev relaxation (``Stencil2D.run_until``) on decomposed
+very thin grids (it takes Neumann sides too); Chebyshev relaxation (``Stencil2D.run_until``) on decomposed
 grids.
 
     python -m cuda_mpi_scratch_amd.models.pcg2d --size 2048x2048 --dtype f64 --source 4.77e-8 --boundary 0 --tol 1e-8
@@ -32,7 +36,7 @@ from dataclasses import asdict, dataclass
 import torch
 
 from .._native import core, hip
-from ..ops import pcg
+from ..ops import cg, pcg
 from ..parallel import DistContext
 from .cg2d import _DTYPES, ConjugateGradient2D, _parse_wh
 
@@ -50,8 +54,10 @@ class PcgConfig:
     coarse_reduction: float = 1e-3
     graph: bool = True
     check_every: int = 2
+    neumann: tuple = ()  # the Neumann sides, any of "top", "bottom", "left", "right"; the others are Dirichlet
 
     def __post_init__(self):
+        self.neumann = cg.neumann_sides(self.neumann)
         if self.dtype not in _DTYPES:
             raise ValueError(f"dtype must be f32 or f64, got {self.dtype!r}")
         if self.width < 1 or self.height < 1:
@@ -62,7 +68,8 @@ class PcgConfig:
             raise ValueError(f"preconditioned CG: nu_pre must equal nu_post (got {self.nu_pre}, {self.nu_post}): CG "
                              "needs a symmetric preconditioner")
         # The plan raises for inadmissible weights and for grids too thin to coarsen.
-        core().pcg_plan_levels(int(self.width), int(self.height), float(self.c_center), float(self.c_neighbor))
+        core().pcg_plan_levels(int(self.width), int(self.height), float(self.c_center), float(self.c_neighbor),
+                               list(self.neumann))
         core().mg_smoother_table(float(self.c_center), float(self.c_neighbor), float(self.smoother_omega),
                                  int(self.nu_pre))
         if not 0.0 < self.coarse_reduction < 1.0:
@@ -82,11 +89,11 @@ class MultigridPcg2D(ConjugateGradient2D):
         self.device = torch.device(device) if device else self.ctx.device
         self.dtype = _DTYPES[cfg.dtype]
         self.iterations_run = 0
-        self.levels = pcg.pcg_plan_levels(cfg.width, cfg.height, cfg.c_center, cfg.c_neighbor)
+        self.levels = pcg.pcg_plan_levels(cfg.width, cfg.height, cfg.c_center, cfg.c_neighbor, cfg.neumann)
         if self.device.type == "cuda":
             with torch.cuda.device(self.device):
                 self.solver = hip().PcgSolver(cfg.width, cfg.height, cfg.dtype, cfg.c_center, cfg.c_neighbor, cfg.nu_pre,
-                                              cfg.smoother_omega, cfg.coarse_reduction, cfg.graph)
+                                              cfg.smoother_omega, cfg.coarse_reduction, cfg.graph, list(cfg.neumann))
             self.geom = self.solver.geom()
         else:
             self.solver = None
@@ -112,7 +119,7 @@ class MultigridPcg2D(ConjugateGradient2D):
             out["history"] = [tuple(h) for h in out["history"]]
         else:
             out = pcg.pcg_reference(self._full, self._g, c.c_center, c.c_neighbor, float(tol), int(max_iters), norm,
-                                    c.nu_pre, c.smoother_omega, c.coarse_reduction)
+                                    c.nu_pre, c.smoother_omega, c.coarse_reduction, neumann=c.neumann)
             self._full = out.pop("full")
         self.iterations_run += out["iterations"]
         return out
@@ -128,8 +135,9 @@ class MultigridPcg2D(ConjugateGradient2D):
         if self.solver is not None:
             return self.solver.note()
         c, last = self.cfg, self.levels[-1]
+        sides = f", Neumann sides {', '.join(c.neumann)}" if c.neumann else ""
         return (f"multigrid-preconditioned CG {c.width}x{c.height}, c_center {c.c_center:g}, c_neighbor "
-                f"{c.c_neighbor:g}, V({c.nu_pre},{c.nu_post}) over {len(self.levels)} levels down to "
+                f"{c.c_neighbor:g}{sides}, V({c.nu_pre},{c.nu_post}) over {len(self.levels)} levels down to "
                 f"{last['width']}x{last['height']}, torch references")
 
 
@@ -149,6 +157,8 @@ def main(argv=None) -> int:
     p.add_argument("--smoother-omega", type=float, default=0.8)
     p.add_argument("--coarse-reduction", type=float, default=1e-3)
     p.add_argument("--check-every", type=int, default=2)
+    p.add_argument("--neumann", default="", metavar="SIDES",
+                   help="comma-separated Neumann (insulated) sides out of top,bottom,left,right; the others are Dirichlet")
     p.add_argument("--no-graph", action="store_true")
     p.add_argument("--device", default=None)
     p.add_argument("--json", default=None)
@@ -156,9 +166,11 @@ def main(argv=None) -> int:
     w, h = _parse_wh(args.size)
     cfg = PcgConfig(width=w, height=h, dtype=args.dtype, c_center=args.c_center, c_neighbor=args.c_neighbor,
                     nu_pre=args.nu, nu_post=args.nu, smoother_omega=args.smoother_omega,
-                    coarse_reduction=args.coarse_reduction, graph=not args.no_graph, check_every=args.check_every)
+                    coarse_reduction=args.coarse_reduction, graph=not args.no_graph, check_every=args.check_every,
+                    neumann=cg.neumann_sides(args.neumann))
     m = MultigridPcg2D(cfg, device=args.device)
-    m.set_boundary(top=args.boundary)
+    if "top" not in cfg.neumann:  # a Neumann top stays insulated
+        m.set_boundary(top=args.boundary)
     m.set_source(args.source)
     if m.solver is not None:  # capture and warm up outside the timed region, then restore the start
         m.solve(args.tol, min(args.max_iters, 2 * args.check_every), args.norm)
@@ -168,7 +180,8 @@ def main(argv=None) -> int:
     out = m.solve(args.tol, args.max_iters, args.norm)
     dt = time.perf_counter() - t0
     rec = {"metric": "pcg2d_solve_s", "value": dt, "config": asdict(cfg), "device": str(m.device), "note": m.note(),
-           "graph": m.graph_status(), "source": args.source, "boundary": args.boundary, "tol": args.tol,
+           "graph": m.graph_status(), "source": args.source, "boundary": args.boundary,
+           "neumann": list(cfg.neumann), "tol": args.tol,
            "norm": out["norm"], "converged": out["converged"], "iterations": out["iterations"],
            "residual": out["residual"], "reason": out["reason"], "restarts": out["restarts"],
            "levels": [(l["width"], l["height"]) for l in m.levels], "history": out["history"][-8:]}

@@ -2,6 +2,7 @@
 JSON line per measurement into OUT, each with the box's name.
 
     python scripts/exp/pcg_measure.py OUT
+    python scripts/exp/pcg_measure.py OUT neumann      (profiles/neumann)
 
 solve : the README's load (f = 1 on the unit square, g = c_neighbor h^2, zero
         boundary and start) in fp64 to l2 <= 1e-8: wall time (host clock around
@@ -14,6 +15,11 @@ split : the time of one iteration at 2048^2: ITERS iterations with tol = 0
         (max_iters = ITERS, one graph launch per 2) for the preconditioned
         solver and for plain CG, whose two kernels are the bodies of pcg_apply
         and pcg_update; the V-cycle's share is the difference.
+neumann : the solve load at 2048^2 for MultigridPcg2D and ConjugateGradient2D
+        with no Neumann side and with the left and the right side insulated,
+        the four solvers interleaved solve by solve in one process; then the
+        time of one iteration of each (the split's recipe). The no-Neumann
+        figures are the ones to hold against profiles/pcg.
 """
 import json
 import os
@@ -122,9 +128,48 @@ def split_case(out, w, h):
                "launches_per_iteration": ms["pcg"].solver.launches_per_iteration()})
 
 
+def neumann_case(out, w, h):
+    sides = {"dirichlet": (), "neumann_left_right": ("left", "right")}
+    ms = {}
+    for tag, nm in sides.items():
+        ms["pcg " + tag] = (MultigridPcg2D(PcgConfig(width=w, height=h, dtype="f64", neumann=nm), device="cuda"),
+                            {"max_iters": 1000}, nm)
+        ms["cg " + tag] = (ConjugateGradient2D(CgConfig(width=w, height=h, dtype="f64", neumann=nm), device="cuda"),
+                           {"max_iters": 100000}, nm)
+    for m, _, _ in ms.values():
+        load(m, w, 0.2)
+    times, last = {k: [] for k in ms}, {}
+    for rep in range(REPEATS + 1):  # the first round is untimed (capture, first touch)
+        for k, (m, kw, _) in ms.items():
+            dt, res = timed_solve(m, **kw)
+            last[k] = res
+            if rep:
+                times[k].append(dt)
+    per = {k: [] for k in ms}
+    for rep in range(REPEATS + 1):
+        for k, (m, _, _) in ms.items():
+            m.set_field(0.0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            res = m.solve(0.0, ITERS, check_every=2)
+            dt = time.perf_counter() - t0
+            assert res["iterations"] == ITERS, res
+            if rep:
+                per[k].append(dt / ITERS)
+    for k, (m, _, nm) in ms.items():
+        res = last[k]
+        emit(out, dict(stats(times[k]), kind="neumann", solver=k.split()[0], neumann=list(nm), width=w, height=h,
+                       tol=TOL, converged=res["converged"], residual=res["residual"], iterations=res["iterations"],
+                       reason=res["reason"], iteration_median_s=statistics.median(per[k]),
+                       iteration_min_s=min(per[k]), iteration_max_s=max(per[k]), note=m.note()))
+
+
 def main():
     out = sys.argv[1]
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    if len(sys.argv) > 2 and sys.argv[2] == "neumann":
+        neumann_case(out, 2048, 2048)
+        return
     solve_case(out, "2048^2 vs CG", 2048, 2048, 0.2, 0.2, "cg")
     solve_case(out, "2047^2 vs multigrid", 2047, 2047, 0.2, 0.2, "multigrid")
     solve_case(out, "3000x1000", 3000, 1000, 0.2, 0.2, None)
