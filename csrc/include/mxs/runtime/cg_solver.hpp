@@ -11,11 +11,13 @@
 // hipGraph (one stream, no branches, an even number of iterations so the p
 // ping-pong closes); eager launches give the same bits.
 //
-// The device's test is on the recursive residual. When it reports convergence
-// the host takes the true residual (stencil5_residual with the source); if
-// that is above tol the solve restarts from cg_start with the iterations
-// already spent counted, and after kCgMaxRestarts restarts it ends "stalled"
-// (the element type's floor).
+// A reported convergence is confirmed on the true residual, else a restart:
+// the host protocol is cg_drive's (mxs/runtime/cg_protocol.hpp).
+//
+// CgSolverBase<T, Scalars> holds what CgSolver and PcgSolver share: the tiles,
+// the scalar blocks, the stream and the graph, the setters and getters, the
+// capture and solve(), which runs cg_drive (mxs/runtime/cg_protocol.hpp). A
+// solver supplies its start launch, its iterations and its note.
 //
 // cfg.neumann names the Neumann sides (mxs/kernels/cg.hpp "GhostSides"): the
 // kernels then read the ghost of such a side as edge + ring (cg_start) or as
@@ -27,7 +29,9 @@
 #include <vector>
 
 #include "mxs/kernels/kernels.hpp"
+#include "mxs/runtime/cg_protocol.hpp"
 #include "mxs/runtime/hip_utils.hpp"
+#include "mxs/runtime/tile_utils.hpp"
 
 namespace mxs {
 
@@ -41,35 +45,15 @@ struct CgConfig {
   std::vector<std::string> neumann;
 };
 
-struct CgResidual {
-  double linf = 0.0, l2 = 0.0;
-  index_t cells = 0;
-};
-
-struct CgSolve {
-  bool converged = false;
-  int iterations = 0;
-  double residual = 0.0;  // the true residual in the chosen norm
-  std::string reason, norm;
-  int restarts = 0;
-  struct Check {
-    int iteration;
-    double linf, l2;  // of the recursive residual, as the device holds it
-  };
-  std::vector<Check> history;
-};
-
-constexpr int kCgMaxRestarts = 3;
-
-template <typename T>
-class CgSolver {
+// Scalars: the device scalar block, kernels::CgScalars or kernels::PcgScalars.
+template <typename T, typename Scalars>
+class CgSolverBase {
  public:
   using value_type = T;
-  explicit CgSolver(const CgConfig& cfg);
-  CgSolver(const CgSolver&) = delete;
-  CgSolver& operator=(const CgSolver&) = delete;
+  CgSolverBase(const CgSolverBase&) = delete;
+  CgSolverBase& operator=(const CgSolverBase&) = delete;
+  virtual ~CgSolverBase() = default;
 
-  const CgConfig& config() const { return cfg_; }
   const TileGeom& geom() const { return geom_; }
 
   // Boundary values of the ring: device pointers to width (top, bottom) or
@@ -81,35 +65,64 @@ class CgSolver {
   void set_field(const T* tile);
   void field(T* tile);
   // Norms of the true residual (A u + g) - u: stencil5_residual with the source.
-  // With a Neumann side it is cg_start's residual (the ghost is edge + ring),
-  // taken into the scratch tiles q and p[1] and a scalar block of its own; a
-  // solve in progress must not call it.
+  // With a Neumann side it is the start kernel's residual (the ghost is edge +
+  // ring), taken into scratch tiles (q; plain CG also p[1]) and a scalar block
+  // of its own; a solve in progress must not call it.
   CgResidual residual();
   CgSolve solve(double tol, int max_iters, const std::string& norm, int check_every);
   // The device scalar block as it stands (a synchronising read).
-  kernels::CgScalars scalars();
+  Scalars scalars() { return read_scalars(); }
   std::string graph_status() const { return graph_status_; }
-  std::string note() const;
+  virtual std::string note() const = 0;
 
- private:
-  void enqueue_iterations(int n, int parity);
-  bool capture(int iters);
-  kernels::CgScalars start(double tol, int max_iters, int norm);
-  kernels::CgScalars read_scalars();
+ protected:
+  // who: the prefix of solve()'s argument errors.
+  CgSolverBase(const char* who, double c_center, double c_neighbor, bool graph, const kernels::GhostSides& sides)
+      : who_(who), c_center_(c_center), c_neighbor_(c_neighbor), graph_on_(graph), sides_(sides) {}
+  // The shared buffers, zeroed on stream_ (not synchronised); partials_ is the solver's to size.
+  void allocate(index_t width, index_t height);
+  kernels::Stencil5Coeffs coeffs() const { return {c_center_, c_neighbor_, false, -1.0}; }
 
-  CgConfig cfg_;
+  // The start kernel into (r, p[0], scalars_) with whatever the solver puts
+  // before it, or, into_scratch, its residual alone into q and residual_scalars_.
+  virtual void launch_start(bool into_scratch) = 0;
+  // Iterations j = parity, parity + 1, ...: j reads p[j % 2] and writes p[(j + 1) % 2].
+  virtual void enqueue_iterations(int n, int parity) = 0;
+
+  const char* who_;
+  double c_center_, c_neighbor_;
+  bool graph_on_;
   kernels::GhostSides sides_;
   TileGeom geom_;
   DeviceBuffer<T> u_, g_, r_, q_, p_[2];
-  DeviceBuffer<kernels::CgScalars> scalars_, residual_scalars_;
-  DeviceBuffer<double> partials_, residual_buf_;
-  DeviceBuffer<unsigned> counter_, residual_counter_;
-  PinnedBuffer<kernels::CgScalars> scalars_host_;
-  PinnedBuffer<double> residual_host_;
+  DeviceBuffer<Scalars> scalars_, residual_scalars_;
+  DeviceBuffer<double> partials_;
+  DeviceBuffer<unsigned> counter_;
+  ResidualReadback readback_;
+  PinnedBuffer<Scalars> scalars_host_;  // [0] the controls on their way up, [1] the readback
   Stream stream_;
   GraphExec graph_;
   int graph_iters_ = 0;
   std::string graph_status_ = "off";
+
+ private:
+  bool capture(int iters);
+  Scalars start(double tol, int max_iters, int norm);
+  Scalars read_scalars();
+};
+
+template <typename T>
+class CgSolver : public CgSolverBase<T, kernels::CgScalars> {
+ public:
+  explicit CgSolver(const CgConfig& cfg);
+  const CgConfig& config() const { return cfg_; }
+  std::string note() const override;
+
+ private:
+  void launch_start(bool into_scratch) override;
+  void enqueue_iterations(int n, int parity) override;
+
+  CgConfig cfg_;
 };
 
 }  // namespace mxs

@@ -6,7 +6,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <chrono>
-
+#include <exception>
 #include <string>
 #include <utility>
 
@@ -181,6 +181,40 @@ class GraphExec {
   hipGraph_t graph_ = nullptr;
   hipGraphExec_t exec_ = nullptr;
 };
+
+// Capture what `enqueue()` puts on `stream` (one stream, no branches) into
+// `graph`, then instantiate and upload it. False, with the graph as it was and
+// the failed step in `status`, when a step fails; "captured" otherwise.
+template <typename Enqueue>
+bool capture_linear(const Stream& stream, GraphExec& graph, std::string& status, Enqueue&& enqueue) {
+  hipGraph_t g = nullptr;
+  if (hipStreamBeginCapture(stream.get(), hipStreamCaptureModeThreadLocal) != hipSuccess) {
+    (void)hipGetLastError();
+    status = "hipStreamBeginCapture failed";
+    return false;
+  }
+  bool ok = true;
+  try {
+    enqueue();
+  } catch (const std::exception& e) {
+    status = std::string("capture failed: ") + e.what();
+    ok = false;
+  }
+  const hipError_t end = hipStreamEndCapture(stream.get(), &g);
+  if (!ok || end != hipSuccess || g == nullptr) {
+    (void)hipGetLastError();
+    if (ok) status = "hipStreamEndCapture failed";
+    if (g) (void)hipGraphDestroy(g);
+    return false;
+  }
+  if (!graph.adopt(g)) {
+    status = "hipGraphInstantiate failed";
+    return false;
+  }
+  graph.upload(stream.get());
+  status = "captured";
+  return true;
+}
 
 inline int current_device() {
   int d = -1;

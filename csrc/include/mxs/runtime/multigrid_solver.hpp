@@ -21,6 +21,7 @@
 
 #include "mxs/kernels/kernels.hpp"
 #include "mxs/runtime/hip_utils.hpp"
+#include "mxs/runtime/tile_utils.hpp"
 
 namespace mxs {
 
@@ -101,9 +102,7 @@ class MultigridSolver {
   bool graph_tried_ = false;
   std::string graph_status_ = "off";
   int launches_ = 0;
-  DeviceBuffer<double> residual_buf_;
-  DeviceBuffer<unsigned> residual_counter_;
-  PinnedBuffer<double> residual_host_;
+  ResidualReadback readback_;
 };
 
 }  // namespace mxs

@@ -40,29 +40,17 @@ struct PcgConfig {
   std::vector<std::string> neumann;  // CgConfig::neumann: the Neumann sides by name
 };
 
+// The setters and getters, residual(), solve() (the same CgSolve record) and
+// scalars() are CgSolverBase's.
 template <typename T>
-class PcgSolver {
+class PcgSolver : public CgSolverBase<T, kernels::PcgScalars> {
  public:
-  using value_type = T;
   explicit PcgSolver(const PcgConfig& cfg);
-  PcgSolver(const PcgSolver&) = delete;
-  PcgSolver& operator=(const PcgSolver&) = delete;
 
   const PcgConfig& config() const { return cfg_; }
-  const TileGeom& geom() const { return geom_; }
   const std::vector<kernels::PcgLevel>& levels() const { return plan_; }
-
-  void set_boundary(const T* top, const T* bottom, const T* left, const T* right);
-  void set_source(const T* tile);
-  void set_field(const T* tile);
-  void field(T* tile);
-  CgResidual residual();
-  // CgSolve: the same record (iterations, the true residual, reason, restarts, history).
-  CgSolve solve(double tol, int max_iters, const std::string& norm, int check_every);
-  kernels::PcgScalars scalars();
-  std::string graph_status() const { return graph_status_; }
   int launches_per_iteration() const { return launches_; }
-  std::string note() const;
+  std::string note() const override;
 
  private:
   struct Level {
@@ -71,28 +59,14 @@ class PcgSolver {
     kernels::MgSweepTable smooth;
   };
   void enqueue_level(size_t k);
-  void enqueue_iterations(int n, int parity);
-  bool capture(int iters);
-  kernels::PcgScalars start(double tol, int max_iters, int norm);
-  kernels::PcgScalars read_scalars();
+  void launch_start(bool into_scratch) override;
+  void enqueue_iterations(int n, int parity) override;
 
   PcgConfig cfg_;
-  kernels::GhostSides sides_;
-  TileGeom geom_;
   std::vector<kernels::PcgLevel> plan_;
   kernels::MgCoarsePlan coarse_;
   std::vector<Level> lv_;
-  DeviceBuffer<T> u_, g_, r_, q_, p_[2];
-  DeviceBuffer<kernels::PcgScalars> scalars_, residual_scalars_;
-  DeviceBuffer<double> partials_, residual_buf_;
-  DeviceBuffer<unsigned> counter_, residual_counter_;
-  PinnedBuffer<kernels::PcgScalars> scalars_host_;
-  PinnedBuffer<double> residual_host_;
-  Stream stream_;
-  GraphExec graph_;
-  int graph_iters_ = 0;
   int launches_ = 0;
-  std::string graph_status_ = "off";
 };
 
 }  // namespace mxs

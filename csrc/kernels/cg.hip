@@ -523,6 +523,68 @@ CgGrid check(const char* who, const TileGeom& g, std::initializer_list<const T*>
   return cg;
 }
 
+// The three launchers, once over the scalar block S (CgScalars: cg_*,
+// PcgScalars: pcg_*). `who` is the public function's name, a literal: it
+// prefixes the check messages and is what last_cg_dispatch() reports.
+// p: the first direction's tile, nullptr with PcgScalars (none is stored).
+template <typename T, typename S>
+void launch_start(const char* who, const T* u, const T* g, T* r, T* p, const TileGeom& geom, Stencil5Coeffs c,
+                  S* scalars, double* partials, unsigned* counter, hipStream_t s, GhostSides sides) {
+  constexpr bool kPcg = std::is_same<S, PcgScalars>::value;
+  const CgGrid cg = kPcg ? check<T>(who, geom, {u, g, r}, scalars, partials, counter)
+                         : check<T>(who, geom, {u, g, r, p}, scalars, partials, counter);
+  if (kPcg) MXS_CHECK(p == nullptr && u != r && g != r && u != g, who << ": u, g and r must be three tiles");
+  else MXS_CHECK(u != r && u != p && g != r && g != p && r != p, who << ": u, g, r and p must be four tiles (r != p)");
+  constexpr int N = CgVec<T>::N;
+  const int vec_ok = geom.pitch % N == 0 && aligned16(u, geom) && aligned16(g, geom) && aligned16(r, geom) &&
+                     (kPcg || aligned16(p, geom));
+  const int mirror = mirror_mask(who, sides);
+  auto* kernel = mirror ? cg_start_kernel<T, S, true> : cg_start_kernel<T, S, false>;
+  kernel<<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(u, g, r, p, geom.pitch, geom.core_offset(), geom.width,
+                                                                  geom.height, cg.gx, cg.band_rows, T(c.center),
+                                                                  T(c.neighbor), vec_ok, mirror, scalars, partials,
+                                                                  counter);
+  g_last_cg = who;
+  MXS_HIP_CHECK_LAUNCH();
+}
+
+// r: the residual, or with PcgScalars z = M r.
+template <typename T, typename S>
+void launch_apply(const char* who, const T* r, const T* p_old, T* p_new, T* q, const TileGeom& geom, Stencil5Coeffs c,
+                  S* scalars, double* partials, unsigned* counter, hipStream_t s, GhostSides sides) {
+  const CgGrid cg = check<T>(who, geom, {r, p_old, p_new, q}, scalars, partials, counter);
+  MXS_CHECK(p_old != p_new, who << ": p_old != p_new (neighbouring workgroups still read p_old: pass the other "
+                                   "buffer of the ping-pong pair)");
+  MXS_CHECK(r != p_new && r != q && p_old != q && p_new != q,
+            who << ": " << (std::is_same<S, PcgScalars>::value ? "z" : "r") << ", p_old, p_new and q must be four tiles");
+  constexpr int N = CgVec<T>::N;
+  const int vec_ok = geom.pitch % N == 0 && aligned16(r, geom) && aligned16(p_old, geom) && aligned16(p_new, geom) &&
+                     aligned16(q, geom);
+  const int mirror = mirror_mask(who, sides);
+  auto* kernel = mirror ? cg_apply_kernel<T, S, true> : cg_apply_kernel<T, S, false>;
+  kernel<<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(r, p_old, p_new, q, geom.pitch, geom.core_offset(),
+                                                                  geom.width, geom.height, cg.gx, cg.band_rows,
+                                                                  T(1.0 - c.center), T(-c.neighbor), vec_ok, mirror,
+                                                                  scalars, partials, counter);
+  g_last_cg = who;
+  MXS_HIP_CHECK_LAUNCH();
+}
+
+template <typename T, typename S>
+void launch_update(const char* who, T* u, T* r, const T* p, const T* q, const TileGeom& geom, S* scalars,
+                   double* partials, unsigned* counter, hipStream_t s) {
+  const CgGrid cg = check<T>(who, geom, {u, r, p, q}, scalars, partials, counter);
+  MXS_CHECK(u != r && u != p && u != q && r != p && r != q && p != q, who << ": u, r, p and q must be four tiles");
+  constexpr int N = CgVec<T>::N;
+  const int vec_ok = geom.pitch % N == 0 && aligned16(u, geom) && aligned16(r, geom) && aligned16(p, geom) &&
+                     aligned16(q, geom);
+  cg_update_kernel<T, S><<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(
+      u, r, p, q, geom.pitch, geom.core_offset(), geom.width, geom.height, cg.gx, cg.band_rows, vec_ok, scalars,
+      partials, counter);
+  g_last_cg = who;
+  MXS_HIP_CHECK_LAUNCH();
+}
+
 }  // namespace
 
 const char* last_cg_dispatch() { return g_last_cg.load(); }
@@ -535,107 +597,38 @@ int cg_grid_size(const TileGeom& g) {
 template <typename T>
 void cg_start(const T* u, const T* g, T* r, T* p, const TileGeom& geom, Stencil5Coeffs c, CgScalars* scalars,
               double* partials, unsigned* counter, hipStream_t s, GhostSides sides) {
-  const CgGrid cg = check<T>("cg_start", geom, {u, g, r, p}, scalars, partials, counter);
-  MXS_CHECK(u != r && u != p && g != r && g != p && r != p, "cg_start: u, g, r and p must be four tiles (r != p)");
-  constexpr int N = CgVec<T>::N;
-  const int vec_ok = geom.pitch % N == 0 && aligned16(u, geom) && aligned16(g, geom) && aligned16(r, geom) &&
-                     aligned16(p, geom);
-  const int mirror = mirror_mask("cg_start", sides);
-  auto* kernel = mirror ? cg_start_kernel<T, CgScalars, true> : cg_start_kernel<T, CgScalars, false>;
-  kernel<<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(u, g, r, p, geom.pitch, geom.core_offset(), geom.width,
-                                                                  geom.height, cg.gx, cg.band_rows, T(c.center),
-                                                                  T(c.neighbor), vec_ok, mirror, scalars, partials,
-                                                                  counter);
-  g_last_cg = "cg_start";
-  MXS_HIP_CHECK_LAUNCH();
+  launch_start<T>("cg_start", u, g, r, p, geom, c, scalars, partials, counter, s, sides);
 }
 
 template <typename T>
 void cg_apply(const T* r, const T* p_old, T* p_new, T* q, const TileGeom& geom, Stencil5Coeffs c, CgScalars* scalars,
               double* partials, unsigned* counter, hipStream_t s, GhostSides sides) {
-  const CgGrid cg = check<T>("cg_apply", geom, {r, p_old, p_new, q}, scalars, partials, counter);
-  MXS_CHECK(p_old != p_new, "cg_apply: p_old != p_new (neighbouring workgroups still read p_old: pass the other "
-                            "buffer of the ping-pong pair)");
-  MXS_CHECK(r != p_new && r != q && p_old != q && p_new != q, "cg_apply: r, p_old, p_new and q must be four tiles");
-  constexpr int N = CgVec<T>::N;
-  const int vec_ok = geom.pitch % N == 0 && aligned16(r, geom) && aligned16(p_old, geom) && aligned16(p_new, geom) &&
-                     aligned16(q, geom);
-  const int mirror = mirror_mask("cg_apply", sides);
-  auto* kernel = mirror ? cg_apply_kernel<T, CgScalars, true> : cg_apply_kernel<T, CgScalars, false>;
-  kernel<<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(r, p_old, p_new, q, geom.pitch, geom.core_offset(),
-                                                                  geom.width, geom.height, cg.gx, cg.band_rows,
-                                                                  T(1.0 - c.center), T(-c.neighbor), vec_ok, mirror,
-                                                                  scalars, partials, counter);
-  g_last_cg = "cg_apply";
-  MXS_HIP_CHECK_LAUNCH();
+  launch_apply<T>("cg_apply", r, p_old, p_new, q, geom, c, scalars, partials, counter, s, sides);
 }
 
 template <typename T>
 void cg_update(T* u, T* r, const T* p, const T* q, const TileGeom& geom, CgScalars* scalars, double* partials,
                unsigned* counter, hipStream_t s) {
-  const CgGrid cg = check<T>("cg_update", geom, {u, r, p, q}, scalars, partials, counter);
-  MXS_CHECK(u != r && u != p && u != q && r != p && r != q && p != q, "cg_update: u, r, p and q must be four tiles");
-  constexpr int N = CgVec<T>::N;
-  const int vec_ok = geom.pitch % N == 0 && aligned16(u, geom) && aligned16(r, geom) && aligned16(p, geom) &&
-                     aligned16(q, geom);
-  cg_update_kernel<T, CgScalars><<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(
-      u, r, p, q, geom.pitch, geom.core_offset(), geom.width, geom.height, cg.gx, cg.band_rows, vec_ok, scalars,
-      partials, counter);
-  g_last_cg = "cg_update";
-  MXS_HIP_CHECK_LAUNCH();
+  launch_update<T>("cg_update", u, r, p, q, geom, scalars, partials, counter, s);
 }
 
 // -------------------------------------------------------- preconditioned CG
 template <typename T>
 void pcg_start(const T* u, const T* g, T* r, const TileGeom& geom, Stencil5Coeffs c, PcgScalars* scalars,
                double* partials, unsigned* counter, hipStream_t s, GhostSides sides) {
-  const CgGrid cg = check<T>("pcg_start", geom, {u, g, r}, scalars, partials, counter);
-  MXS_CHECK(u != r && g != r && u != g, "pcg_start: u, g and r must be three tiles");
-  constexpr int N = CgVec<T>::N;
-  const int vec_ok = geom.pitch % N == 0 && aligned16(u, geom) && aligned16(g, geom) && aligned16(r, geom);
-  const int mirror = mirror_mask("pcg_start", sides);
-  auto* kernel = mirror ? cg_start_kernel<T, PcgScalars, true> : cg_start_kernel<T, PcgScalars, false>;
-  kernel<<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(u, g, r, static_cast<T*>(nullptr), geom.pitch,
-                                                                  geom.core_offset(), geom.width, geom.height, cg.gx,
-                                                                  cg.band_rows, T(c.center), T(c.neighbor), vec_ok, mirror,
-                                                                  scalars, partials, counter);
-  g_last_cg = "pcg_start";
-  MXS_HIP_CHECK_LAUNCH();
+  launch_start<T>("pcg_start", u, g, r, static_cast<T*>(nullptr), geom, c, scalars, partials, counter, s, sides);
 }
 
 template <typename T>
 void pcg_apply(const T* z, const T* p_old, T* p_new, T* q, const TileGeom& geom, Stencil5Coeffs c, PcgScalars* scalars,
                double* partials, unsigned* counter, hipStream_t s, GhostSides sides) {
-  const CgGrid cg = check<T>("pcg_apply", geom, {z, p_old, p_new, q}, scalars, partials, counter);
-  MXS_CHECK(p_old != p_new, "pcg_apply: p_old != p_new (neighbouring workgroups still read p_old: pass the other "
-                            "buffer of the ping-pong pair)");
-  MXS_CHECK(z != p_new && z != q && p_old != q && p_new != q, "pcg_apply: z, p_old, p_new and q must be four tiles");
-  constexpr int N = CgVec<T>::N;
-  const int vec_ok = geom.pitch % N == 0 && aligned16(z, geom) && aligned16(p_old, geom) && aligned16(p_new, geom) &&
-                     aligned16(q, geom);
-  const int mirror = mirror_mask("pcg_apply", sides);
-  auto* kernel = mirror ? cg_apply_kernel<T, PcgScalars, true> : cg_apply_kernel<T, PcgScalars, false>;
-  kernel<<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(z, p_old, p_new, q, geom.pitch, geom.core_offset(),
-                                                                  geom.width, geom.height, cg.gx, cg.band_rows,
-                                                                  T(1.0 - c.center), T(-c.neighbor), vec_ok, mirror,
-                                                                  scalars, partials, counter);
-  g_last_cg = "pcg_apply";
-  MXS_HIP_CHECK_LAUNCH();
+  launch_apply<T>("pcg_apply", z, p_old, p_new, q, geom, c, scalars, partials, counter, s, sides);
 }
 
 template <typename T>
 void pcg_update(T* u, T* r, const T* p, const T* q, const TileGeom& geom, PcgScalars* scalars, double* partials,
                 unsigned* counter, hipStream_t s) {
-  const CgGrid cg = check<T>("pcg_update", geom, {u, r, p, q}, scalars, partials, counter);
-  MXS_CHECK(u != r && u != p && u != q && r != p && r != q && p != q, "pcg_update: u, r, p and q must be four tiles");
-  constexpr int N = CgVec<T>::N;
-  const int vec_ok = geom.pitch % N == 0 && aligned16(u, geom) && aligned16(r, geom) && aligned16(p, geom) &&
-                     aligned16(q, geom);
-  cg_update_kernel<T, PcgScalars><<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(
-      u, r, p, q, geom.pitch, geom.core_offset(), geom.width, geom.height, cg.gx, cg.band_rows, vec_ok, scalars,
-      partials, counter);
-  g_last_cg = "pcg_update";
-  MXS_HIP_CHECK_LAUNCH();
+  launch_update<T>("pcg_update", u, r, p, q, geom, scalars, partials, counter, s);
 }
 
 #define MXS_CG_INSTANTIATE(T)                                                                                       \

@@ -92,46 +92,30 @@ kernels::BoxWeights make_box(int radius, const std::vector<float>& w) {
   return b;
 }
 
-// Type-erased solver handle so Python sees one class.
-struct SolverHandle {
+// Type-erased solver handle so Python sees one class per solver.
+template <template <class> class Solver>
+struct TypedHandle {
   DType dt;
-  std::unique_ptr<StencilSolver<float>> f;
-  std::unique_ptr<StencilSolver<double>> d;
+  std::unique_ptr<Solver<float>> f;
+  std::unique_ptr<Solver<double>> d;
   template <typename F>
   auto visit(F&& fn) {
     return dt == DType::F32 ? fn(*f) : fn(*d);
   }
-};
-
-struct MultigridHandle {
-  DType dt;
-  std::unique_ptr<MultigridSolver<float>> f;
-  std::unique_ptr<MultigridSolver<double>> d;
-  template <typename F>
-  auto visit(F&& fn) {
-    return dt == DType::F32 ? fn(*f) : fn(*d);
+  // The solver of `dtype` from its config struct.
+  template <typename Config>
+  static std::unique_ptr<TypedHandle> make(const std::string& dtype, const Config& cfg) {
+    auto h = std::make_unique<TypedHandle>();
+    h->dt = parse_dtype(dtype);
+    if (h->dt == DType::F32) h->f = std::make_unique<Solver<float>>(cfg);
+    else h->d = std::make_unique<Solver<double>>(cfg);
+    return h;
   }
 };
-
-struct CgHandle {
-  DType dt;
-  std::unique_ptr<CgSolver<float>> f;
-  std::unique_ptr<CgSolver<double>> d;
-  template <typename F>
-  auto visit(F&& fn) {
-    return dt == DType::F32 ? fn(*f) : fn(*d);
-  }
-};
-
-struct PcgHandle {
-  DType dt;
-  std::unique_ptr<PcgSolver<float>> f;
-  std::unique_ptr<PcgSolver<double>> d;
-  template <typename F>
-  auto visit(F&& fn) {
-    return dt == DType::F32 ? fn(*f) : fn(*d);
-  }
-};
+using SolverHandle = TypedHandle<StencilSolver>;
+using MultigridHandle = TypedHandle<MultigridSolver>;
+using CgHandle = TypedHandle<CgSolver>;
+using PcgHandle = TypedHandle<PcgSolver>;
 
 // Ghost codes (top, bottom, left, right) from Python; set reflect flags turn a far code of 0 into -1.
 kernels::GhostSides ghost_sides(const std::array<int, 4>& c, bool reflect_rows = false, bool reflect_cols = false) {
@@ -142,10 +126,12 @@ kernels::GhostSides ghost_sides(const std::array<int, 4>& c, bool reflect_rows =
 }
 const std::array<int, 4> kNoSides{0, 0, 0, 0};
 
-py::dict pcg_scalars_dict(const kernels::PcgScalars& s) {
+// CgScalars or PcgScalars ("rz" is the latter's alone).
+template <typename S>
+py::dict scalars_dict(const S& s) {
   py::dict d;
   d["rr"] = s.rr;
-  d["rz"] = s.rz;
+  if constexpr (std::is_same<S, kernels::PcgScalars>::value) d["rz"] = s.rz;
   d["pq"] = s.pq;
   d["alpha"] = s.alpha;
   d["beta"] = s.beta;
@@ -158,19 +144,96 @@ py::dict pcg_scalars_dict(const kernels::PcgScalars& s) {
   return d;
 }
 
-py::dict cg_scalars_dict(const kernels::CgScalars& s) {
+// CgResidual or MultigridResidual.
+template <typename R>
+py::dict residual_dict(const R& r) {
   py::dict d;
-  d["rr"] = s.rr;
-  d["pq"] = s.pq;
-  d["alpha"] = s.alpha;
-  d["beta"] = s.beta;
-  d["linf"] = s.linf;
-  d["tol"] = s.tol;
-  d["iteration"] = s.iteration;
-  d["max_iters"] = s.max_iters;
-  d["norm"] = s.norm;
-  d["status"] = s.status;
+  d["linf"] = r.linf;
+  d["l2"] = r.l2;
+  d["cells"] = r.cells;
   return d;
+}
+
+py::dict cg_solve_dict(const CgSolve& r) {
+  py::dict d;
+  d["converged"] = r.converged;
+  d["iterations"] = r.iterations;
+  d["residual"] = r.residual;
+  d["reason"] = r.reason;
+  d["norm"] = r.norm;
+  d["restarts"] = r.restarts;
+  py::list hist;
+  for (const auto& c : r.history) hist.append(py::make_tuple(c.iteration, c.linf, c.l2));
+  d["history"] = hist;
+  return d;
+}
+
+// What the single-GPU Poisson solvers (MultigridSolver, CgSolver, PcgSolver) offer alike.
+template <typename Handle>
+void def_poisson_methods(py::class_<Handle>& c) {
+  c.def("geom", [](Handle& h) { return h.visit([](auto& s) { return s.geom(); }); })
+      .def(
+          "set_boundary",
+          [](Handle& h, std::uintptr_t top, std::uintptr_t bottom, std::uintptr_t left, std::uintptr_t right) {
+            h.visit([&](auto& s) {
+              using T = typename std::decay_t<decltype(s)>::value_type;
+              s.set_boundary(ptr<T>(top), ptr<T>(bottom), ptr<T>(left), ptr<T>(right));
+            });
+          },
+          py::arg("top") = 0, py::arg("bottom") = 0, py::arg("left") = 0, py::arg("right") = 0,
+          "device pointers to width (top, bottom) / height (left, right) boundary values; 0 leaves a side as it is")
+      .def(
+          "set_source",
+          [](Handle& h, std::uintptr_t tile) {
+            h.visit([&](auto& s) {
+              using T = typename std::decay_t<decltype(s)>::value_type;
+              s.set_source(ptr<T>(tile));
+            });
+          },
+          py::arg("tile") = 0, "a device tile of geom() whose core holds g, or 0 (g = 0)")
+      .def("set_field",
+           [](Handle& h, std::uintptr_t tile) {
+             h.visit([&](auto& s) {
+               using T = typename std::decay_t<decltype(s)>::value_type;
+               s.set_field(ptr<T>(tile));
+             });
+           })
+      .def("field",
+           [](Handle& h, std::uintptr_t tile) {
+             h.visit([&](auto& s) {
+               using T = typename std::decay_t<decltype(s)>::value_type;
+               s.field(ptr<T>(tile));
+             });
+           })
+      .def("residual",
+           [](Handle& h) {
+             const auto r = [&h] {
+               py::gil_scoped_release nogil;
+               return h.visit([](auto& s) { return s.residual(); });
+             }();
+             return residual_dict(r);
+           })
+      .def("graph_status", [](Handle& h) { return h.visit([](auto& s) { return s.graph_status(); }); })
+      .def("note", [](Handle& h) { return h.visit([](auto& s) { return s.note(); }); });
+}
+
+// CgSolver and PcgSolver: the solve and the scalar block.
+template <typename Handle>
+void def_cg_methods(py::class_<Handle>& c, int max_iters, int check_every, const char* solve_doc) {
+  c.def(
+       "solve",
+       [](Handle& h, double tol, int max_iters, const std::string& norm, int check_every) {
+         CgSolve r;
+         {
+           py::gil_scoped_release nogil;
+           r = h.visit([&](auto& s) { return s.solve(tol, max_iters, norm, check_every); });
+         }
+         return cg_solve_dict(r);
+       },
+       py::arg("tol"), py::arg("max_iters") = max_iters, py::arg("norm") = "l2", py::arg("check_every") = check_every,
+       solve_doc)
+      .def("scalars", [](Handle& h) { return h.visit([](auto& s) { return scalars_dict(s.scalars()); }); },
+           "the device scalar block as a dict (a synchronising read)");
 }
 
 struct ExchangerHandle {
@@ -1093,7 +1156,8 @@ PYBIND11_MODULE(_mxs_hip, m) {
   m.def("last_multigrid_dispatch", [] { return std::string(kernels::last_multigrid_dispatch()); },
         "the kernel the most recent multigrid launcher ran ('' before the first)");
 
-  py::class_<MultigridHandle>(m, "MultigridSolver")
+  py::class_<MultigridHandle> multigrid_solver(m, "MultigridSolver");
+  multigrid_solver
       .def(py::init([](index_t w, index_t h, const std::string& dt, double c0, double c1, int nu_pre, int nu_post,
                        double omega, double coarse_reduction, bool graph) {
              MultigridConfig cfg;
@@ -1106,16 +1170,11 @@ PYBIND11_MODULE(_mxs_hip, m) {
              cfg.smoother_omega = omega;
              cfg.coarse_reduction = coarse_reduction;
              cfg.graph = graph;
-             auto h_ = std::make_unique<MultigridHandle>();
-             h_->dt = parse_dtype(dt);
-             if (h_->dt == DType::F32) h_->f = std::make_unique<MultigridSolver<float>>(cfg);
-             else h_->d = std::make_unique<MultigridSolver<double>>(cfg);
-             return h_;
+             return MultigridHandle::make(dt, cfg);
            }),
            py::arg("width"), py::arg("height"), py::arg("dtype") = "f64", py::arg("c_center") = 0.2,
            py::arg("c_neighbor") = 0.2, py::arg("nu_pre") = 2, py::arg("nu_post") = 2, py::arg("smoother_omega") = 0.8,
            py::arg("coarse_reduction") = 1e-3, py::arg("graph") = true)
-      .def("geom", [](MultigridHandle& h) { return h.visit([](auto& s) { return s.geom(); }); })
       .def("levels",
            [](MultigridHandle& h) {
              std::vector<std::pair<long long, long long>> out;
@@ -1123,52 +1182,6 @@ PYBIND11_MODULE(_mxs_hip, m) {
                for (const auto& l : s.levels()) out.emplace_back(l.width, l.height);
              });
              return out;
-           })
-      .def(
-          "set_boundary",
-          [](MultigridHandle& h, std::uintptr_t top, std::uintptr_t bottom, std::uintptr_t left, std::uintptr_t right) {
-            h.visit([&](auto& s) {
-              using T = typename std::decay_t<decltype(s)>::value_type;
-              s.set_boundary(ptr<T>(top), ptr<T>(bottom), ptr<T>(left), ptr<T>(right));
-            });
-          },
-          py::arg("top") = 0, py::arg("bottom") = 0, py::arg("left") = 0, py::arg("right") = 0,
-          "device pointers to width (top, bottom) / height (left, right) boundary values; 0 leaves a side as it is")
-      .def(
-          "set_source",
-          [](MultigridHandle& h, std::uintptr_t tile) {
-            h.visit([&](auto& s) {
-              using T = typename std::decay_t<decltype(s)>::value_type;
-              s.set_source(ptr<T>(tile));
-            });
-          },
-          py::arg("tile") = 0, "a device tile of geom() whose core holds g, or 0 (g = 0)")
-      .def("set_field",
-           [](MultigridHandle& h, std::uintptr_t tile) {
-             h.visit([&](auto& s) {
-               using T = typename std::decay_t<decltype(s)>::value_type;
-               s.set_field(ptr<T>(tile));
-             });
-           })
-      .def("field",
-           [](MultigridHandle& h, std::uintptr_t tile) {
-             h.visit([&](auto& s) {
-               using T = typename std::decay_t<decltype(s)>::value_type;
-               s.field(ptr<T>(tile));
-             });
-           })
-      .def("residual",
-           [](MultigridHandle& h) {
-             MultigridResidual r;
-             {
-               py::gil_scoped_release nogil;
-               r = h.visit([](auto& s) { return s.residual(); });
-             }
-             py::dict d;
-             d["linf"] = r.linf;
-             d["l2"] = r.l2;
-             d["cells"] = r.cells;
-             return d;
            })
       .def("vcycle", [](MultigridHandle& h, int n) { h.visit([&](auto& s) { s.vcycle(n); }); }, py::arg("n") = 1,
            py::call_guard<py::gil_scoped_release>())
@@ -1194,9 +1207,8 @@ PYBIND11_MODULE(_mxs_hip, m) {
           py::arg("tol"), py::arg("max_cycles") = 50, py::arg("norm") = "l2",
           "residual() + vcycle(1) until the norm is <= tol, max_cycles ran, the norm is not finite, or no new best "
           "residual for 3 consecutive cycles ('stalled')")
-      .def("graph_status", [](MultigridHandle& h) { return h.visit([](auto& s) { return s.graph_status(); }); })
-      .def("launches_per_cycle", [](MultigridHandle& h) { return h.visit([](auto& s) { return s.launches_per_cycle(); }); })
-      .def("note", [](MultigridHandle& h) { return h.visit([](auto& s) { return s.note(); }); });
+      .def("launches_per_cycle", [](MultigridHandle& h) { return h.visit([](auto& s) { return s.launches_per_cycle(); }); });
+  def_poisson_methods(multigrid_solver);
 
   // ------------------------------------------------------- conjugate gradients
   // The launchers take the scalar block (CG_SCALARS_BYTES: doubles rr, pq, alpha,
@@ -1257,98 +1269,24 @@ PYBIND11_MODULE(_mxs_hip, m) {
   m.def("last_cg_dispatch", [] { return std::string(kernels::last_cg_dispatch()); },
         "the kernel the most recent CG launcher ran ('' before the first)");
 
-  py::class_<CgHandle>(m, "CgSolver")
-      .def(py::init([](index_t w, index_t h, const std::string& dt, double c0, double c1, bool graph,
-                       const std::vector<std::string>& neumann) {
-             CgConfig cfg;
-             cfg.neumann = neumann;
-             cfg.width = w;
-             cfg.height = h;
-             cfg.c_center = c0;
-             cfg.c_neighbor = c1;
-             cfg.graph = graph;
-             auto h_ = std::make_unique<CgHandle>();
-             h_->dt = parse_dtype(dt);
-             if (h_->dt == DType::F32) h_->f = std::make_unique<CgSolver<float>>(cfg);
-             else h_->d = std::make_unique<CgSolver<double>>(cfg);
-             return h_;
-           }),
-           py::arg("width"), py::arg("height"), py::arg("dtype") = "f64", py::arg("c_center") = 0.2,
-           py::arg("c_neighbor") = 0.2, py::arg("graph") = true, py::arg("neumann") = std::vector<std::string>{})
-      .def("geom", [](CgHandle& h) { return h.visit([](auto& s) { return s.geom(); }); })
-      .def(
-          "set_boundary",
-          [](CgHandle& h, std::uintptr_t top, std::uintptr_t bottom, std::uintptr_t left, std::uintptr_t right) {
-            h.visit([&](auto& s) {
-              using T = typename std::decay_t<decltype(s)>::value_type;
-              s.set_boundary(ptr<T>(top), ptr<T>(bottom), ptr<T>(left), ptr<T>(right));
-            });
-          },
-          py::arg("top") = 0, py::arg("bottom") = 0, py::arg("left") = 0, py::arg("right") = 0,
-          "device pointers to width (top, bottom) / height (left, right) boundary values; 0 leaves a side as it is")
-      .def(
-          "set_source",
-          [](CgHandle& h, std::uintptr_t tile) {
-            h.visit([&](auto& s) {
-              using T = typename std::decay_t<decltype(s)>::value_type;
-              s.set_source(ptr<T>(tile));
-            });
-          },
-          py::arg("tile") = 0, "a device tile of geom() whose core holds g, or 0 (g = 0)")
-      .def("set_field",
-           [](CgHandle& h, std::uintptr_t tile) {
-             h.visit([&](auto& s) {
-               using T = typename std::decay_t<decltype(s)>::value_type;
-               s.set_field(ptr<T>(tile));
-             });
-           })
-      .def("field",
-           [](CgHandle& h, std::uintptr_t tile) {
-             h.visit([&](auto& s) {
-               using T = typename std::decay_t<decltype(s)>::value_type;
-               s.field(ptr<T>(tile));
-             });
-           })
-      .def("residual",
-           [](CgHandle& h) {
-             CgResidual r;
-             {
-               py::gil_scoped_release nogil;
-               r = h.visit([](auto& s) { return s.residual(); });
-             }
-             py::dict d;
-             d["linf"] = r.linf;
-             d["l2"] = r.l2;
-             d["cells"] = r.cells;
-             return d;
-           })
-      .def(
-          "solve",
-          [](CgHandle& h, double tol, int max_iters, const std::string& norm, int check_every) {
-            CgSolve r;
-            {
-              py::gil_scoped_release nogil;
-              r = h.visit([&](auto& s) { return s.solve(tol, max_iters, norm, check_every); });
-            }
-            py::dict d;
-            d["converged"] = r.converged;
-            d["iterations"] = r.iterations;
-            d["residual"] = r.residual;
-            d["reason"] = r.reason;
-            d["norm"] = r.norm;
-            d["restarts"] = r.restarts;
-            py::list hist;
-            for (const auto& c : r.history) hist.append(py::make_tuple(c.iteration, c.linf, c.l2));
-            d["history"] = hist;
-            return d;
-          },
-          py::arg("tol"), py::arg("max_iters") = 10000, py::arg("norm") = "l2", py::arg("check_every") = 32,
-          "cg_start, then blocks of check_every iterations and a read of the device scalars until the device stops; a "
-          "reported convergence is confirmed on the true residual (else a restart, 'stalled' after 3)")
-      .def("scalars", [](CgHandle& h) { return cg_scalars_dict(h.visit([](auto& s) { return s.scalars(); })); },
-           "the device scalar block as a dict (a synchronising read)")
-      .def("graph_status", [](CgHandle& h) { return h.visit([](auto& s) { return s.graph_status(); }); })
-      .def("note", [](CgHandle& h) { return h.visit([](auto& s) { return s.note(); }); });
+  py::class_<CgHandle> cg_solver(m, "CgSolver");
+  cg_solver.def(py::init([](index_t w, index_t h, const std::string& dt, double c0, double c1, bool graph,
+                            const std::vector<std::string>& neumann) {
+                  CgConfig cfg;
+                  cfg.neumann = neumann;
+                  cfg.width = w;
+                  cfg.height = h;
+                  cfg.c_center = c0;
+                  cfg.c_neighbor = c1;
+                  cfg.graph = graph;
+                  return CgHandle::make(dt, cfg);
+                }),
+                py::arg("width"), py::arg("height"), py::arg("dtype") = "f64", py::arg("c_center") = 0.2,
+                py::arg("c_neighbor") = 0.2, py::arg("graph") = true, py::arg("neumann") = std::vector<std::string>{});
+  def_poisson_methods(cg_solver);
+  def_cg_methods(cg_solver, 10000, 32,
+                 "cg_start, then blocks of check_every iterations and a read of the device scalars until the device "
+                 "stops; a reported convergence is confirmed on the true residual (else a restart, 'stalled' after 3)");
 
   // ---------------------------------------------------------- preconditioned CG
   // The scalar block is PCG_SCALARS_BYTES: doubles rr, rz, pq, alpha, beta, linf,
@@ -1470,7 +1408,8 @@ PYBIND11_MODULE(_mxs_hip, m) {
   m.def("last_pcg_dispatch", [] { return std::string(kernels::last_pcg_dispatch()); },
         "the kernel the most recent preconditioner launcher ran ('' before the first)");
 
-  py::class_<PcgHandle>(m, "PcgSolver")
+  py::class_<PcgHandle> pcg_solver(m, "PcgSolver");
+  pcg_solver
       .def(py::init([](index_t w, index_t h, const std::string& dt, double c0, double c1, int nu, double omega,
                        double coarse_reduction, bool graph, const std::vector<std::string>& neumann) {
              PcgConfig cfg;
@@ -1483,17 +1422,12 @@ PYBIND11_MODULE(_mxs_hip, m) {
              cfg.smoother_omega = omega;
              cfg.coarse_reduction = coarse_reduction;
              cfg.graph = graph;
-             auto h_ = std::make_unique<PcgHandle>();
-             h_->dt = parse_dtype(dt);
-             if (h_->dt == DType::F32) h_->f = std::make_unique<PcgSolver<float>>(cfg);
-             else h_->d = std::make_unique<PcgSolver<double>>(cfg);
-             return h_;
+             return PcgHandle::make(dt, cfg);
            }),
            py::arg("width"), py::arg("height"), py::arg("dtype") = "f64", py::arg("c_center") = 0.2,
            py::arg("c_neighbor") = 0.2, py::arg("nu") = 2, py::arg("smoother_omega") = 0.8,
            py::arg("coarse_reduction") = 1e-3, py::arg("graph") = true,
            py::arg("neumann") = std::vector<std::string>{})
-      .def("geom", [](PcgHandle& h) { return h.visit([](auto& s) { return s.geom(); }); })
       .def("levels",
            [](PcgHandle& h) {
              py::list out;
@@ -1503,78 +1437,11 @@ PYBIND11_MODULE(_mxs_hip, m) {
              });
              return out;
            })
-      .def(
-          "set_boundary",
-          [](PcgHandle& h, std::uintptr_t top, std::uintptr_t bottom, std::uintptr_t left, std::uintptr_t right) {
-            h.visit([&](auto& s) {
-              using T = typename std::decay_t<decltype(s)>::value_type;
-              s.set_boundary(ptr<T>(top), ptr<T>(bottom), ptr<T>(left), ptr<T>(right));
-            });
-          },
-          py::arg("top") = 0, py::arg("bottom") = 0, py::arg("left") = 0, py::arg("right") = 0)
-      .def(
-          "set_source",
-          [](PcgHandle& h, std::uintptr_t tile) {
-            h.visit([&](auto& s) {
-              using T = typename std::decay_t<decltype(s)>::value_type;
-              s.set_source(ptr<T>(tile));
-            });
-          },
-          py::arg("tile") = 0)
-      .def("set_field",
-           [](PcgHandle& h, std::uintptr_t tile) {
-             h.visit([&](auto& s) {
-               using T = typename std::decay_t<decltype(s)>::value_type;
-               s.set_field(ptr<T>(tile));
-             });
-           })
-      .def("field",
-           [](PcgHandle& h, std::uintptr_t tile) {
-             h.visit([&](auto& s) {
-               using T = typename std::decay_t<decltype(s)>::value_type;
-               s.field(ptr<T>(tile));
-             });
-           })
-      .def("residual",
-           [](PcgHandle& h) {
-             CgResidual r;
-             {
-               py::gil_scoped_release nogil;
-               r = h.visit([](auto& s) { return s.residual(); });
-             }
-             py::dict d;
-             d["linf"] = r.linf;
-             d["l2"] = r.l2;
-             d["cells"] = r.cells;
-             return d;
-           })
-      .def(
-          "solve",
-          [](PcgHandle& h, double tol, int max_iters, const std::string& norm, int check_every) {
-            CgSolve r;
-            {
-              py::gil_scoped_release nogil;
-              r = h.visit([&](auto& s) { return s.solve(tol, max_iters, norm, check_every); });
-            }
-            py::dict d;
-            d["converged"] = r.converged;
-            d["iterations"] = r.iterations;
-            d["residual"] = r.residual;
-            d["reason"] = r.reason;
-            d["norm"] = r.norm;
-            d["restarts"] = r.restarts;
-            py::list hist;
-            for (const auto& c : r.history) hist.append(py::make_tuple(c.iteration, c.linf, c.l2));
-            d["history"] = hist;
-            return d;
-          },
-          py::arg("tol"), py::arg("max_iters") = 1000, py::arg("norm") = "l2", py::arg("check_every") = 2,
-          "pcg_start, then blocks of check_every iterations (V-cycle, pcg_apply, pcg_update) and a read of the device "
-          "scalars until the device stops; a reported convergence is confirmed on the true residual")
-      .def("scalars", [](PcgHandle& h) { return pcg_scalars_dict(h.visit([](auto& s) { return s.scalars(); })); })
-      .def("graph_status", [](PcgHandle& h) { return h.visit([](auto& s) { return s.graph_status(); }); })
-      .def("launches_per_iteration", [](PcgHandle& h) { return h.visit([](auto& s) { return s.launches_per_iteration(); }); })
-      .def("note", [](PcgHandle& h) { return h.visit([](auto& s) { return s.note(); }); });
+      .def("launches_per_iteration", [](PcgHandle& h) { return h.visit([](auto& s) { return s.launches_per_iteration(); }); });
+  def_poisson_methods(pcg_solver);
+  def_cg_methods(pcg_solver, 1000, 2,
+                 "pcg_start, then blocks of check_every iterations (V-cycle, pcg_apply, pcg_update) and a read of the "
+                 "device scalars until the device stops; a reported convergence is confirmed on the true residual");
 
   // ------------------------------------------------------------------ ping-pong
   py::enum_<PingPongMode>(m, "PingPongMode")

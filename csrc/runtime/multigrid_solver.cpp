@@ -29,10 +29,7 @@ MultigridSolver<T>::MultigridSolver(const MultigridConfig& cfg) : cfg_(cfg) {
       MXS_HIP_CHECK(hipMemsetAsync(b->get(), 0, b->bytes(), stream_.get()));
     }
   }
-  const index_t grid = kernels::residual_grid_size(lv_[0].geom);
-  residual_buf_.reset(2 + 2 * grid);
-  residual_counter_.reset(1);
-  residual_host_.reset(2);
+  readback_.reset(lv_[0].geom);
   // The coarse solve once, outside any capture (it raises its LDS limit on
   // first use); g = 0 gives e = 0.
   Level& c = lv_.back();
@@ -42,21 +39,7 @@ MultigridSolver<T>::MultigridSolver(const MultigridConfig& cfg) : cfg_(cfg) {
 
 template <typename T>
 void MultigridSolver<T>::set_boundary(const T* top, const T* bottom, const T* left, const T* right) {
-  const TileGeom& g = lv_[0].geom;
-  const index_t off = g.core_offset();
-  for (int k = 0; k < 2; ++k) {
-    T* u = lv_[0].u[k].get();
-    if (top) MXS_HIP_CHECK(hipMemcpyAsync(u + off - g.pitch, top, size_t(g.width) * sizeof(T), hipMemcpyDeviceToDevice, stream_.get()));
-    if (bottom)
-      MXS_HIP_CHECK(hipMemcpyAsync(u + off + g.height * g.pitch, bottom, size_t(g.width) * sizeof(T),
-                                   hipMemcpyDeviceToDevice, stream_.get()));
-    if (left)
-      MXS_HIP_CHECK(hipMemcpy2DAsync(u + off - 1, size_t(g.pitch) * sizeof(T), left, sizeof(T), sizeof(T), size_t(g.height),
-                                     hipMemcpyDeviceToDevice, stream_.get()));
-    if (right)
-      MXS_HIP_CHECK(hipMemcpy2DAsync(u + off + g.width, size_t(g.pitch) * sizeof(T), right, sizeof(T), sizeof(T),
-                                     size_t(g.height), hipMemcpyDeviceToDevice, stream_.get()));
-  }
+  for (int k = 0; k < 2; ++k) copy_ring_sides(lv_[0].u[k].get(), lv_[0].geom, top, bottom, left, right, stream_.get());
   stream_.sync();
 }
 
@@ -87,18 +70,8 @@ void MultigridSolver<T>::field(T* tile) {
 template <typename T>
 MultigridResidual MultigridSolver<T>::residual() {
   const Level& l = lv_[0];
-  auto* norms = reinterpret_cast<kernels::ResidualNorms*>(residual_buf_.get());
-  kernels::Stencil5Coeffs c{cfg_.c_center, cfg_.c_neighbor, false, -1.0};
-  kernels::stencil5_residual<T>(l.u[0].get(), l.geom, c, norms, residual_buf_.get() + 2, residual_counter_.get(),
-                                stream_.get(), l.g.get());
-  MXS_HIP_CHECK(hipMemcpyAsync(residual_host_.get(), norms, sizeof(kernels::ResidualNorms), hipMemcpyDeviceToHost,
-                               stream_.get()));
-  stream_.spin_sync();
-  MultigridResidual r;
-  r.linf = residual_host_.get()[0];
-  r.l2 = std::sqrt(residual_host_.get()[1]);
-  r.cells = l.geom.width * l.geom.height;
-  return r;
+  return readback_.template read<MultigridResidual>(l.u[0].get(), l.g.get(), l.geom, cfg_.c_center, cfg_.c_neighbor,
+                                                    stream_);
 }
 
 template <typename T>
@@ -134,33 +107,7 @@ void MultigridSolver<T>::enqueue_cycle() {
 template <typename T>
 bool MultigridSolver<T>::capture() {
   graph_tried_ = true;
-  hipGraph_t g = nullptr;
-  if (hipStreamBeginCapture(stream_.get(), hipStreamCaptureModeThreadLocal) != hipSuccess) {
-    (void)hipGetLastError();
-    graph_status_ = "hipStreamBeginCapture failed";
-    return false;
-  }
-  bool ok = true;
-  try {
-    enqueue_cycle();
-  } catch (const std::exception& e) {
-    graph_status_ = std::string("capture failed: ") + e.what();
-    ok = false;
-  }
-  const hipError_t end = hipStreamEndCapture(stream_.get(), &g);
-  if (!ok || end != hipSuccess || g == nullptr) {
-    (void)hipGetLastError();
-    if (ok) graph_status_ = "hipStreamEndCapture failed";
-    if (g) (void)hipGraphDestroy(g);
-    return false;
-  }
-  if (!graph_.adopt(g)) {
-    graph_status_ = "hipGraphInstantiate failed";
-    return false;
-  }
-  graph_.upload(stream_.get());
-  graph_status_ = "captured";
-  return true;
+  return capture_linear(stream_, graph_, graph_status_, [&] { enqueue_cycle(); });
 }
 
 template <typename T>

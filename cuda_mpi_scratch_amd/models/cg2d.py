@@ -62,26 +62,36 @@ class CgConfig:
 
 
 class ConjugateGradient2D:
+    # What a subclass on the same tiles and native calls (MultigridPcg2D) replaces.
+    _why_one_process = ("decomposed grids are out of scope, they would need a halo exchange of the direction and an "
+                        "all-reduce of the scalars")
+
     def __init__(self, cfg: CgConfig, ctx: DistContext | None = None, device: str | None = None):
         self.cfg = cfg
         self.ctx = ctx or DistContext()
         if self.ctx.world_size > 1:
-            raise ValueError(f"ConjugateGradient2D runs in one process (world size {self.ctx.world_size}): decomposed "
-                             "grids are out of scope, they would need a halo exchange of the direction and an all-reduce "
-                             "of the scalars")
+            raise ValueError(f"{type(self).__name__} runs in one process (world size {self.ctx.world_size}): "
+                             f"{self._why_one_process}")
         self.device = torch.device(device) if device else self.ctx.device
         self.dtype = _DTYPES[cfg.dtype]
         self.iterations_run = 0
         if self.device.type == "cuda":
             with torch.cuda.device(self.device):
-                self.solver = hip().CgSolver(cfg.width, cfg.height, cfg.dtype, cfg.c_center, cfg.c_neighbor, cfg.graph,
-                                             list(cfg.neumann))
+                self.solver = self._native_solver()
             self.geom = self.solver.geom()
         else:
             self.solver = None
             self.geom = core().TileGeom.compact(cfg.width, cfg.height, 1, 1)
             self._full = torch.zeros((cfg.height + 2, cfg.width + 2), dtype=self.dtype)
             self._g = torch.zeros((cfg.height, cfg.width), dtype=self.dtype)
+
+    def _native_solver(self):
+        c = self.cfg
+        return hip().CgSolver(c.width, c.height, c.dtype, c.c_center, c.c_neighbor, c.graph, list(c.neumann))
+
+    def _reference_solve(self, tol: float, max_iters: int, norm: str) -> dict:
+        c = self.cfg
+        return cg.cg_reference(self._full, self._g, c.c_center, c.c_neighbor, tol, max_iters, norm, neumann=c.neumann)
 
     # ------------------------------------------------------------------ set-up
     def _core_of(self, tile: torch.Tensor) -> torch.Tensor:
@@ -209,13 +219,11 @@ class ConjugateGradient2D:
         every = self.cfg.check_every if check_every is None else int(check_every)
         if every < 1:
             raise ValueError(f"solve: check_every must be >= 1, got {every}")
-        c = self.cfg
         if self.solver is not None:
             out = dict(self.solver.solve(float(tol), int(max_iters), norm, every))
             out["history"] = [tuple(h) for h in out["history"]]
         else:
-            out = cg.cg_reference(self._full, self._g, c.c_center, c.c_neighbor, float(tol), int(max_iters), norm,
-                                  neumann=c.neumann)
+            out = self._reference_solve(float(tol), int(max_iters), norm)
             self._full = out.pop("full")
         self.iterations_run += out["iterations"]
         return out
@@ -245,28 +253,37 @@ def _parse_wh(s: str) -> tuple[int, int]:
     return int(w), int(h)
 
 
-def main(argv=None) -> int:
-    p = argparse.ArgumentParser(description="conjugate gradients for the fixed-edge solve u = A u + g (MI355X-native)")
-    p.add_argument("--size", default="2048x2048", help="core WxH, any sides >= 1")
+def solver_parser(description: str, size_help: str, max_iters: int, check_every: int) -> argparse.ArgumentParser:
+    """The flags cg2d and pcg2d share; a module adds its own before it calls ``run_main``."""
+    p = argparse.ArgumentParser(description=description)
+    p.add_argument("--size", default="2048x2048", help=size_help)
     p.add_argument("--dtype", default="f64", choices=list(_DTYPES))
     p.add_argument("--source", type=float, default=None, metavar="Q", help="a constant source term g = Q")
     p.add_argument("--boundary", type=float, default=1.0, help="the top edge's value (the other edges hold 0)")
     p.add_argument("--tol", type=float, default=1e-8)
-    p.add_argument("--max-iters", type=int, default=100000)
+    p.add_argument("--max-iters", type=int, default=max_iters)
     p.add_argument("--norm", default="l2", choices=["linf", "l2"])
     p.add_argument("--c-center", type=float, default=0.2)
     p.add_argument("--c-neighbor", type=float, default=0.2)
-    p.add_argument("--check-every", type=int, default=32)
+    p.add_argument("--check-every", type=int, default=check_every)
     p.add_argument("--neumann", default="", metavar="SIDES",
                    help="comma-separated Neumann (insulated) sides out of top,bottom,left,right; the others are Dirichlet")
     p.add_argument("--no-graph", action="store_true")
     p.add_argument("--device", default=None)
     p.add_argument("--json", default=None)
+    return p
+
+
+def run_main(p: argparse.ArgumentParser, argv, metric: str, model, config, extra=lambda args: {},
+             record_extra=lambda m: {}) -> int:
+    """Parse, build ``model(config(...))``, warm up, time one solve and emit the record.
+    ``extra(args)``: the module's own config fields; ``record_extra(m)``: its own record keys."""
     args = p.parse_args(argv)
     w, h = _parse_wh(args.size)
-    cfg = CgConfig(width=w, height=h, dtype=args.dtype, c_center=args.c_center, c_neighbor=args.c_neighbor,
-                   graph=not args.no_graph, check_every=args.check_every, neumann=cg.neumann_sides(args.neumann))
-    m = ConjugateGradient2D(cfg, device=args.device)
+    cfg = config(width=w, height=h, dtype=args.dtype, c_center=args.c_center, c_neighbor=args.c_neighbor,
+                 graph=not args.no_graph, check_every=args.check_every, neumann=cg.neumann_sides(args.neumann),
+                 **extra(args))
+    m = model(cfg, device=args.device)
     if "top" not in cfg.neumann:  # a Neumann top stays insulated
         m.set_boundary(top=args.boundary)
     m.set_source(args.source)
@@ -277,17 +294,23 @@ def main(argv=None) -> int:
     t0 = time.perf_counter()
     out = m.solve(args.tol, args.max_iters, args.norm)
     dt = time.perf_counter() - t0
-    rec = {"metric": "cg2d_solve_s", "value": dt, "config": asdict(cfg), "device": str(m.device), "note": m.note(),
+    rec = {"metric": metric, "value": dt, "config": asdict(cfg), "device": str(m.device), "note": m.note(),
            "graph": m.graph_status(), "source": args.source, "boundary": args.boundary,
            "neumann": list(cfg.neumann), "tol": args.tol,
            "norm": out["norm"], "converged": out["converged"], "iterations": out["iterations"],
            "residual": out["residual"], "reason": out["reason"], "restarts": out["restarts"],
-           "history": out["history"][-8:]}
+           **record_extra(m), "history": out["history"][-8:]}
     print(json.dumps(rec))
     if args.json:
         with open(args.json, "a") as f:
             f.write(json.dumps(rec) + "\n")
     return 0
+
+
+def main(argv=None) -> int:
+    p = solver_parser("conjugate gradients for the fixed-edge solve u = A u + g (MI355X-native)",
+                      "core WxH, any sides >= 1", max_iters=100000, check_every=32)
+    return run_main(p, argv, "cg2d_solve_s", ConjugateGradient2D, CgConfig)
 
 
 if __name__ == "__main__":

@@ -1,9 +1,9 @@
 // Host-only unit tests of the C++ core ("Unit tests"): region
 // algebra, accessor indexing, Cartesian neighbour tables, halo-plan
 // aggregation/ordering, the collective decision statistics, the
-// interior-first chunk schedule, the pipeline form rule, the fast-form guard
-// and the solver's call plan. Run by ctest and by tests/test_cpp_unit.py (and
-// under host ASan/UBSan by scripts/cpu_sanitize.sh).
+// interior-first chunk schedule, the pipeline form rule, the fast-form guard,
+// the solver's call plan and the CG solvers' host protocol. Run by ctest and by
+// tests/test_cpp_unit.py (and under host ASan/UBSan by scripts/cpu_sanitize.sh).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -14,6 +14,7 @@
 #include <vector>
 #include <set>
 #include <sstream>
+#include <stdexcept>
 #include <string>
 
 #include "mxs/grid/layout.hpp"
@@ -24,6 +25,7 @@
 #include "mxs/kernels/kernels.hpp"
 #include "mxs/kernels/pipe_form.hpp"
 #include "mxs/runtime/call_plan.hpp"
+#include "mxs/runtime/cg_protocol.hpp"
 #include "mxs/runtime/decision.hpp"
 #include "mxs/topo/cart.hpp"
 
@@ -420,7 +422,189 @@ static void test_call_plan() {
   EXPECT(g[0].count == 0 && g[1].count == 0);
 }
 
+// A scripted device for cg_drive: runs[k] is what the scalar block reads after
+// the k-th start and after each of its blocks, truths the true residuals in the
+// order they are asked for.
+struct CgScript {
+  std::vector<std::vector<CgProgress>> runs;
+  std::vector<CgResidual> truths;
+  struct StartArgs {
+    double tol;
+    int remaining, norm_id;
+  };
+  std::vector<StartArgs> starts;
+  int steps = 0, truths_taken = 0;
+  size_t at = 0;
+
+  CgSolve drive(double tol, int max_iters, const std::string& norm = "l2", int check_every = 2,
+                const char* who = "conjugate gradients") {
+    return cg_drive(
+        who, tol, max_iters, norm, check_every,
+        [&](double t, int remaining, int norm_id) {
+          starts.push_back({t, remaining, norm_id});
+          at = 0;
+          return runs.at(starts.size() - 1).at(at++);
+        },
+        [&] {
+          ++steps;
+          return runs.at(starts.size() - 1).at(at++);
+        },
+        [&] { return truths.at(size_t(truths_taken++)); });
+  }
+};
+
+static bool history_is(const CgSolve& s, std::initializer_list<CgSolve::Check> want) {
+  if (s.history.size() != want.size()) return false;
+  size_t i = 0;
+  for (const CgSolve::Check& w : want) {
+    const CgSolve::Check& h = s.history[i++];
+    if (h.iteration != w.iteration || h.linf != w.linf || h.l2 != w.l2) return false;
+  }
+  return true;
+}
+
+template <typename F>
+static std::string thrown_by(F&& f) {
+  try {
+    f();
+  } catch (const std::invalid_argument& e) {
+    return e.what();
+  }
+  return "(nothing thrown)";
+}
+
+static void test_cg_protocol() {
+  using kernels::kCgBreakdown;
+  using kernels::kCgConverged;
+  using kernels::kCgMaxIters;
+  using kernels::kCgRunning;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  // rr values are squares, so the history's l2 = sqrt(rr) is exact.
+  {  // converged at the first read: one entry at iteration 0, the true residual reported
+    CgScript s;
+    s.runs = {{{kCgConverged, 0, 0.25, 0.375}}};
+    s.truths = {{0.0625, 0.125, 6}};
+    const CgSolve r = s.drive(1.0, 100);
+    EXPECT(r.converged && r.iterations == 0 && r.restarts == 0 && r.norm == "l2");
+    EXPECT(r.reason == "converged: l2 residual <= tol");
+    EXPECT(r.residual == 0.125);  // the true one, not sqrt(rr) = 0.5
+    EXPECT(history_is(r, {{0, 0.375, 0.5}}));
+    EXPECT(s.starts.size() == 1 && s.starts[0].tol == 1.0 && s.starts[0].remaining == 100 &&
+           s.starts[0].norm_id == kernels::kCgNormL2);
+    EXPECT(s.steps == 0 && s.truths_taken == 1);
+  }
+  {  // one history entry per block after the start's; linf picks the other norm
+    CgScript s;
+    s.runs = {{{kCgRunning, 0, 16.0, 3.0}, {kCgRunning, 2, 4.0, 1.5}, {kCgConverged, 3, 0.25, 0.25}}};
+    s.truths = {{0.3125, 0.5, 6}};
+    const CgSolve r = s.drive(0.4, 100, "linf");
+    EXPECT(r.converged && r.iterations == 3 && r.restarts == 0 && r.norm == "linf");
+    EXPECT(r.reason == "converged: linf residual <= tol" && r.residual == 0.3125);
+    EXPECT(history_is(r, {{0, 3.0, 4.0}, {2, 1.5, 2.0}, {3, 0.25, 0.5}}));
+    EXPECT(s.starts[0].norm_id == kernels::kCgNormLinf && s.steps == 2 && s.truths_taken == 1);
+  }
+  {  // the device converged, the true residual did not: one restart, then converged
+    CgScript s;
+    s.runs = {{{kCgRunning, 0, 16.0, 3.0}, {kCgRunning, 2, 4.0, 1.5}, {kCgConverged, 4, 0.25, 0.25}},
+              {{kCgRunning, 0, 9.0, 2.0}, {kCgConverged, 2, 0.0625, 0.125}}};
+    s.truths = {{2.0, 3.0, 6}, {0.125, 0.25, 6}};
+    const CgSolve r = s.drive(1.0, 10);
+    EXPECT(r.converged && r.iterations == 6 && r.restarts == 1 && r.residual == 0.25);
+    EXPECT(r.reason == "converged: l2 residual <= tol");
+    EXPECT(history_is(r, {{0, 3.0, 4.0}, {2, 1.5, 2.0}, {4, 0.25, 0.5}, {4, 2.0, 3.0}, {6, 0.125, 0.25}}));
+    EXPECT(s.starts.size() == 2 && s.starts[0].remaining == 10 && s.starts[1].remaining == 6 && s.starts[1].tol == 1.0);
+    EXPECT(s.steps == 3 && s.truths_taken == 2);
+  }
+  {  // the same failure more than kCgMaxRestarts times: stalled
+    CgScript s;
+    s.runs.assign(4, {{kCgRunning, 0, 16.0, 3.0}, {kCgConverged, 2, 0.25, 0.25}});
+    s.truths.assign(4, {2.0, 3.0, 6});
+    const CgSolve r = s.drive(1.0, 1000);
+    EXPECT(!r.converged && r.reason == "stalled" && r.restarts == 3 && kCgMaxRestarts == 3);
+    EXPECT(r.iterations == 8 && r.residual == 3.0);
+    EXPECT(history_is(r, {{0, 3.0, 4.0}, {2, 0.25, 0.5}, {2, 3.0, 4.0}, {4, 0.25, 0.5}, {4, 3.0, 4.0}, {6, 0.25, 0.5},
+                          {6, 3.0, 4.0}, {8, 0.25, 0.5}}));
+    EXPECT(s.starts.size() == 4 && s.starts[3].remaining == 994 && s.truths_taken == 4);
+  }
+  {  // the device converged, the true residual did not, nothing remains: no restart
+    CgScript s;
+    s.runs = {{{kCgRunning, 0, 16.0, 3.0}, {kCgConverged, 2, 0.25, 0.25}}};
+    s.truths = {{2.0, 3.0, 6}};
+    const CgSolve r = s.drive(1.0, 2);
+    EXPECT(!r.converged && r.reason == "max_iters reached" && r.restarts == 0 && r.iterations == 2 && r.residual == 3.0);
+    EXPECT(history_is(r, {{0, 3.0, 4.0}, {2, 0.25, 0.5}}));
+    EXPECT(s.starts.size() == 1 && s.truths_taken == 1);
+  }
+  {  // the device ran out of iterations: the true residual once, at the end
+    CgScript s;
+    s.runs = {{{kCgRunning, 0, 16.0, 3.0}, {kCgRunning, 2, 9.0, 2.0}, {kCgMaxIters, 4, 4.0, 1.0}}};
+    s.truths = {{1.5, 2.5, 6}};
+    const CgSolve r = s.drive(1.0, 4);
+    EXPECT(!r.converged && r.reason == "max_iters reached" && r.restarts == 0 && r.iterations == 4 && r.residual == 2.5);
+    EXPECT(history_is(r, {{0, 3.0, 4.0}, {2, 2.0, 3.0}, {4, 1.0, 2.0}}));
+    EXPECT(s.starts.size() == 1 && s.steps == 2 && s.truths_taken == 1);
+  }
+  {  // p . L p not positive, the residual finite
+    CgScript s;
+    s.runs = {{{kCgRunning, 0, 16.0, 3.0}, {kCgBreakdown, 1, 9.0, 2.0}}};
+    s.truths = {{1.5, 2.5, 6}};
+    const CgSolve r = s.drive(1.0, 50);
+    EXPECT(!r.converged && r.reason == "breakdown" && r.iterations == 1 && r.residual == 2.5 && r.restarts == 0);
+    EXPECT(history_is(r, {{0, 3.0, 4.0}, {1, 2.0, 3.0}}));
+    EXPECT(s.truths_taken == 1);
+  }
+  {  // the same status with a NaN rr, and with a NaN linf
+    CgScript s;
+    s.runs = {{{kCgRunning, 0, 16.0, 3.0}, {kCgBreakdown, 1, nan, 2.0}}};
+    s.truths = {{nan, nan, 6}};
+    CgSolve r = s.drive(1.0, 50);
+    EXPECT(!r.converged && r.reason == "non-finite residual" && r.iterations == 1 && std::isnan(r.residual));
+    EXPECT(r.history.size() == 2 && r.history[1].iteration == 1 && r.history[1].linf == 2.0 && std::isnan(r.history[1].l2));
+    CgScript t;
+    t.runs = {{{kCgBreakdown, 0, 4.0, nan}}};
+    t.truths = {{1.0, 1.0, 6}};
+    r = t.drive(1.0, 50);
+    EXPECT(!r.converged && r.reason == "non-finite residual" && t.steps == 0);
+  }
+  {  // a reported convergence whose true residual is not finite (either norm's)
+    CgScript s;
+    s.runs = {{{kCgConverged, 0, 0.25, 0.25}}};
+    s.truths = {{0.5, nan, 6}};
+    CgSolve r = s.drive(1.0, 50);
+    EXPECT(!r.converged && r.reason == "non-finite residual" && r.restarts == 0 && std::isnan(r.residual));
+    EXPECT(s.starts.size() == 1 && s.truths_taken == 1);
+    CgScript t;
+    t.runs = {{{kCgConverged, 0, 0.25, 0.25}}};
+    t.truths = {{nan, 0.5, 6}};
+    r = t.drive(1.0, 50);  // l2 is finite and below tol, linf is not finite
+    EXPECT(!r.converged && r.reason == "non-finite residual" && r.residual == 0.5);
+  }
+  {  // max_iters == 0: the start kernel runs (it reports kCgMaxIters), no block does
+    CgScript s;
+    s.runs = {{{kCgMaxIters, 0, 16.0, 3.0}}};
+    s.truths = {{3.0, 4.0, 6}};
+    const CgSolve r = s.drive(1.0, 0);
+    EXPECT(!r.converged && r.reason == "max_iters reached" && r.iterations == 0 && r.residual == 4.0);
+    EXPECT(history_is(r, {{0, 3.0, 4.0}}));
+    EXPECT(s.starts.size() == 1 && s.starts[0].remaining == 0 && s.steps == 0 && s.truths_taken == 1);
+  }
+  {  // bad arguments: invalid_argument with the solver's prefix, nothing launched
+    CgScript s;
+    EXPECT(thrown_by([&] { s.drive(1.0, 10, "l1"); }) == "conjugate gradients: norm must be 'linf' or 'l2', got 'l1'");
+    EXPECT(thrown_by([&] { s.drive(1.0, 10, "l1", 2, "preconditioned CG"); }) ==
+           "preconditioned CG: norm must be 'linf' or 'l2', got 'l1'");
+    const std::string args = ": solve needs tol >= 0, max_iters >= 0 and check_every >= 1";
+    EXPECT(thrown_by([&] { s.drive(nan, 10); }) == "conjugate gradients" + args);
+    EXPECT(thrown_by([&] { s.drive(-1e-9, 10); }) == "conjugate gradients" + args);
+    EXPECT(thrown_by([&] { s.drive(1.0, -1); }) == "conjugate gradients" + args);
+    EXPECT(thrown_by([&] { s.drive(1.0, 10, "l2", 0); }) == "conjugate gradients" + args);
+    EXPECT(thrown_by([&] { s.drive(1.0, 10, "linf", 0, "preconditioned CG"); }) == "preconditioned CG" + args);
+    EXPECT(s.starts.empty() && s.steps == 0 && s.truths_taken == 0);
+  }
+}
+
 int main() {
+  test_cg_protocol();
   test_call_plan();
   test_pipe_form();
   test_fast_form_verdict();
