@@ -2,7 +2,8 @@
 arithmetic: every operation of the kernels' chains is evaluated on
 ``fractions.Fraction`` operands and rounded once, to the nearer of the two
 neighbouring values of the element type (ties to even), never through a double.
-This is what "bitwise" in tests/test_gpu_one_step.py rests on."""
+This is what "bitwise" in tests/test_gpu_one_step.py rests on and, through the
+level reference with unequal pairs, in tests/test_gpu_level_passes.py."""
 import struct
 from fractions import Fraction
 
@@ -110,6 +111,52 @@ def test_block_reference_equals_the_level_reference_on_the_core(dtype, steps):
     big = _field((H + 2 * steps + 3, W + 2 * steps + 2), dtype, 40 + steps)
     per = ops.stencil5_exact_periodic_reference(big, steps, c0, c1)[steps:-steps, steps:-steps]
     assert int((_bit_view(ops.stencil5_exact_block_reference(big, steps, c0, c1)) != _bit_view(per)).sum()) == 0
+
+
+LEVELS = ([0.3, -1.75, 2.5], [0.15, 0.6875, -0.4])  # three unequal pairs: which level takes which is visible
+
+
+def _held_levels_rational(full, center, neighbor, hold, ring, dtype):
+    """The contract of ops.jacobi_held_levels_reference on lists and Fractions:
+    level l updates every cell but the array's outermost ring with pair l, then
+    the cells outside the core on a held side take their input values back."""
+    u0 = full.double().tolist()
+    rows, cols = len(u0), len(u0[0])
+    u = [row[:] for row in u0]
+    for c0, c1 in zip(center, neighbor):
+        new = [row[:] for row in u]
+        for y in range(1, rows - 1):
+            for x in range(1, cols - 1):
+                new[y][x] = _cell(u[y][x], u[y - 1][x], u[y + 1][x], u[y][x - 1], u[y][x + 1], c0, c1, dtype)
+        for y in range(rows):
+            for x in range(cols):
+                if ((hold & ops.HOLD_TOP and y < ring) or (hold & ops.HOLD_BOTTOM and y >= rows - ring)
+                        or (hold & ops.HOLD_LEFT and x < ring) or (hold & ops.HOLD_RIGHT and x >= cols - ring)):
+                    new[y][x] = u0[y][x]
+        u = new
+    return u
+
+
+@pytest.mark.parametrize("hold", [0, 15])
+@pytest.mark.parametrize("dtype", ["f32", "f64"])
+def test_level_reference_equals_rational_arithmetic_with_unequal_levels(dtype, hold):
+    """A 7 x 9 core with a ring of 3 and 3 levels of unequal pairs: the whole
+    array, ring included, bit for bit; and the table is taken in its order (the
+    reversed table gives another core)."""
+    ring = 3
+    center, neighbor = LEVELS
+    full = _field((7 + 2 * ring, 9 + 2 * ring), dtype, 31)
+    got = ops.jacobi_held_levels_reference(full, center, neighbor, hold=hold)
+    assert got.shape == full.shape and got.dtype == DT[dtype]
+    assert _differing(got, _held_levels_rational(full, center, neighbor, hold, ring, dtype), dtype) == 0
+    back = ops.jacobi_held_levels_reference(full, center[::-1], neighbor[::-1], hold=hold)
+    assert _differing(back, _held_levels_rational(full, center[::-1], neighbor[::-1], hold, ring, dtype), dtype) == 0
+    core = (slice(ring, -ring), slice(ring, -ring))
+    assert int((_bit_view(got[core]) != _bit_view(back[core])).sum()) > 0
+    if hold == 15:  # the ring is held: input values at every level
+        outside = torch.ones(full.shape, dtype=torch.bool)
+        outside[core] = False
+        assert torch.equal(_bit_view(got)[outside], _bit_view(full)[outside])
 
 
 def test_block_reference_needs_a_core():
