@@ -18,7 +18,7 @@
 //          cg_start, cg_apply, cg_update (conjugate gradients with fused dot products)
 //          pcg_start, pcg_apply, pcg_update (the same bodies for preconditioned CG) kernels/cg.hip
 //          mgp_smooth, mgp_residual_restrict, mgp_prolong_add, mgp_coarse_solve (the any-size
-//          V-cycle preconditioner)            kernels/pcg_precond.hip
+//          V-cycle preconditioner: the same kernels with ghost codes)  kernels/multigrid.hip
 //                                                kernels/cg.hip
 #pragma once
 
@@ -415,7 +415,7 @@ void cg_update(T* u, T* r, const T* p, const T* q, const TileGeom& geom, CgScala
 // the first); not updated by graph replays.
 const char* last_cg_dispatch();
 
-// ---------------------------- preconditioned CG (kernels/cg.hip, kernels/pcg_precond.hip)
+// ---------------------------- preconditioned CG (kernels/cg.hip, kernels/multigrid.hip)
 // CG preconditioned by one any-size V-cycle (pcg.hpp; docs/ARCHITECTURE.md
 // "Preconditioned CG"). The pcg_* kernels are the cg_* bodies on a PcgScalars
 // block: the same expressions, grids, partials (2 * cg_grid_size(g) doubles) and

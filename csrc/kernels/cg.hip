@@ -7,7 +7,7 @@
 // The same three bodies, instantiated on PcgScalars, are pcg_start, pcg_apply
 // and pcg_update of multigrid-preconditioned CG (mxs/kernels/pcg.hpp): z = M r
 // stands for r in apply, alpha = rz / pq, and beta comes from the
-// preconditioner's dot epilogue (pcg_device.hpp) instead of update.
+// preconditioner's dot epilogue (multigrid_device.hpp) instead of update.
 //
 // Shape (that of residual.hip):
 //   * a lane owns one 16-byte vector (4 fp32 / 2 fp64 columns), a wave a strip

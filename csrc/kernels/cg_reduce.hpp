@@ -1,5 +1,5 @@
 // The deterministic grid reduction of the CG kernels (cg.hip) and of the
-// preconditioner's dot epilogue (pcg_precond.hip): per-workgroup partials and a
+// preconditioner's dot epilogue (multigrid.hip): per-workgroup partials and a
 // last-block finish in a fixed order (agent-scope release before the ticket,
 // acquire after it, partials read on the vector path); no floating-point
 // atomics, and no workgroup waits on another. Workgroups of kCgBlock threads.

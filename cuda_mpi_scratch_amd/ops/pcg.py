@@ -13,7 +13,7 @@ positive-definite operator (``nu_pre == nu_post``); it need not converge alone.
 
 The references work on plain 2-D arrays: ``full`` is the core plus a depth-1
 ring, ``(H + 2, W + 2)``; ``g, r, z, p, q, e`` are core sized. Every expression is
-a rounding contract with ``csrc/kernels/pcg_device.hpp`` and ``cg.hip``, and each
+a rounding contract with ``csrc/kernels/multigrid_device.hpp`` and ``cg.hip``, and each
 is the one of ``ops.multigrid`` / ``ops.cg``; on a reflecting side the ghost is
 ``-c`` (exact) wherever a sweep or a residual reads it, the ring there is never
 read. Sums (``rz = sum r z`` beside CG's) are float64 and differ from the
