@@ -17,6 +17,7 @@
 //                                                kernels/multigrid.hip
 //          cg_start, cg_apply, cg_update (conjugate gradients with fused dot products)
 //          pcg_start, pcg_apply, pcg_update (the same bodies for preconditioned CG) kernels/cg.hip
+//          cg_heat_start, pcg_heat_start (the start of an implicit heat step: right-hand side and residual in one pass)
 //          mgp_smooth, mgp_residual_restrict, mgp_prolong_add, mgp_coarse_solve (the any-size
 //          V-cycle preconditioner: the same kernels with ghost codes)  kernels/multigrid.hip
 //                                                kernels/cg.hip
@@ -32,6 +33,7 @@
 #include "mxs/kernels/cg.hpp"
 #include "mxs/kernels/chunk_schedule.hpp"
 #include "mxs/kernels/fixed_edge_split.hpp"
+#include "mxs/kernels/heat.hpp"
 #include "mxs/kernels/multigrid.hpp"
 #include "mxs/kernels/pcg.hpp"
 #include "mxs/kernels/pipe_form.hpp"
@@ -439,6 +441,26 @@ void pcg_apply(const T* z, const T* p_old, T* p_new, T* q, const TileGeom& geom,
 template <typename T>
 void pcg_update(T* u, T* r, const T* p, const T* q, const TileGeom& geom, PcgScalars* scalars, double* partials,
                 unsigned* counter, hipStream_t s);
+
+// ------------------------------------------- implicit heat steps (kernels/cg.hip)
+// The start of one theta-scheme step (heat.hpp; docs/ARCHITECTURE.md "Implicit
+// heat steps"): cg_start / pcg_start with the step's right-hand side made in the
+// same pass over u. With S = (n + s) + (w + e), ghosts as cg_start reads them
+// (a mirror ghost is edge + ring), and the coefficients rounded to T once:
+//   g = fma(T(b), S, T(a) c);  with a source  g = g + T(s) q  (product rounded, then the sum)
+//   r = (fma(T(c1), S, T(0) c) + g) - c
+// so r, rr and linf are bit for bit those of cg_start on (u, the stored g) with
+// weights (0, c1): same grid, same partials. Writes the cores of g and r (and p
+// = r for cg_heat_start); reads u with its ring and the core of q. q == nullptr
+// selects the no-source kernels, which never read q. The last workgroup
+// finishes the scalar block as cg_start / pcg_start do. ("cg_heat_start",
+// "pcg_heat_start" in last_cg_dispatch().)
+template <typename T>
+void cg_heat_start(const T* u, const T* q, T* g, T* r, T* p, const TileGeom& geom, const HeatCoeffs& hc,
+                   CgScalars* scalars, double* partials, unsigned* counter, hipStream_t s, GhostSides sides = {});
+template <typename T>
+void pcg_heat_start(const T* u, const T* q, T* g, T* r, const TileGeom& geom, const HeatCoeffs& hc,
+                    PcgScalars* scalars, double* partials, unsigned* counter, hipStream_t s, GhostSides sides = {});
 
 // The preconditioner's kernels: the multigrid kernels for any size, with the
 // reflecting ghost of pcg.hpp. reflect_rows: the ghost row `height` reads as

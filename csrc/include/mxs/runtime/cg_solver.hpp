@@ -17,7 +17,9 @@
 // CgSolverBase<T, Scalars> holds what CgSolver and PcgSolver share: the tiles,
 // the scalar blocks, the stream and the graph, the setters and getters, the
 // capture and solve(), which runs cg_drive (mxs/runtime/cg_protocol.hpp). A
-// solver supplies its start launch, its iterations and its note.
+// solver supplies its start launch, its iterations and its note. step() is
+// solve() for one implicit heat step (mxs/kernels/heat.hpp): its first start
+// launch is the fused heat start, which also makes the right-hand side g.
 //
 // cfg.neumann names the Neumann sides (mxs/kernels/cg.hpp "GhostSides"): the
 // kernels then read the ghost of such a side as edge + ring (cg_start) or as
@@ -70,6 +72,19 @@ class CgSolverBase {
   // of its own; a solve in progress must not call it.
   CgResidual residual();
   CgSolve solve(double tol, int max_iters, const std::string& norm, int check_every);
+  // One implicit heat step u -> u' (mxs/kernels/heat.hpp): solve() with one
+  // difference, the first run's start launch is the fused kernel (cg_heat_start
+  // / pcg_heat_start), which makes the step's right-hand side from u as it
+  // stands (and the step source) and writes it into g: every step overwrites
+  // g, so set_source() is not the way to give a step its source. Restart runs,
+  // residual() and the confirmation on the true residual use the ordinary start
+  // on the stored g, so after a step residual() is that step's true residual.
+  // Throws unless the solver's (c_center, c_neighbor) are exactly (0, hc.c1).
+  CgSolve step(const kernels::HeatCoeffs& hc, double tol, int max_iters, const std::string& norm, int check_every);
+  // q = dt f of the steps to come: a device tile of geom() whose core holds it
+  // (copied into a tile of the solver's own, allocated on first use), or nullptr
+  // for none: the steps then run the no-source kernel. It is not g.
+  void set_step_source(const T* tile);
   // The device scalar block as it stands (a synchronising read).
   Scalars scalars() { return read_scalars(); }
   std::string graph_status() const { return graph_status_; }
@@ -86,6 +101,8 @@ class CgSolverBase {
   // The start kernel into (r, p[0], scalars_) with whatever the solver puts
   // before it, or, into_scratch, its residual alone into q and residual_scalars_.
   virtual void launch_start(bool into_scratch) = 0;
+  // The fused start of a heat step into (g, r, p[0], scalars_); q: the step source or nullptr.
+  virtual void launch_heat_start(const kernels::HeatCoeffs& hc, const T* q) = 0;
   // Iterations j = parity, parity + 1, ...: j reads p[j % 2] and writes p[(j + 1) % 2].
   virtual void enqueue_iterations(int n, int parity) = 0;
 
@@ -95,6 +112,8 @@ class CgSolverBase {
   kernels::GhostSides sides_;
   TileGeom geom_;
   DeviceBuffer<T> u_, g_, r_, q_, p_[2];
+  DeviceBuffer<T> step_q_;  // the step source, allocated by the first set_step_source(tile)
+  bool step_source_ = false;
   DeviceBuffer<Scalars> scalars_, residual_scalars_;
   DeviceBuffer<double> partials_;
   DeviceBuffer<unsigned> counter_;
@@ -107,7 +126,9 @@ class CgSolverBase {
 
  private:
   bool capture(int iters);
-  Scalars start(double tol, int max_iters, int norm);
+  // heat: the run starts with the fused heat start instead of launch_start(false).
+  Scalars start(double tol, int max_iters, int norm, const kernels::HeatCoeffs* heat);
+  CgSolve drive(const kernels::HeatCoeffs* heat, double tol, int max_iters, const std::string& norm, int check_every);
   Scalars read_scalars();
 };
 
@@ -120,6 +141,7 @@ class CgSolver : public CgSolverBase<T, kernels::CgScalars> {
 
  private:
   void launch_start(bool into_scratch) override;
+  void launch_heat_start(const kernels::HeatCoeffs& hc, const T* q) override;
   void enqueue_iterations(int n, int parity) override;
 
   CgConfig cfg_;

@@ -60,6 +60,7 @@ class PcgSolver : public CgSolverBase<T, kernels::PcgScalars> {
   };
   void enqueue_level(size_t k);
   void launch_start(bool into_scratch) override;
+  void launch_heat_start(const kernels::HeatCoeffs& hc, const T* q) override;
   void enqueue_iterations(int n, int parity) override;
 
   PcgConfig cfg_;

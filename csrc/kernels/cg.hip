@@ -8,6 +8,10 @@
 // and pcg_update of multigrid-preconditioned CG (mxs/kernels/pcg.hpp): z = M r
 // stands for r in apply, alpha = rz / pq, and beta comes from the
 // preconditioner's dot epilogue (multigrid_device.hpp) instead of update.
+// cg_heat_start / pcg_heat_start are the start kernel of an implicit heat step
+// (mxs/kernels/heat.hpp): the step's right-hand side g is made and stored in
+// the pass that takes the first residual, a kernel of its own so that
+// cg_start_kernel's instantiations stay as they are.
 //
 // Shape (that of residual.hip):
 //   * a lane owns one 16-byte vector (4 fp32 / 2 fp64 columns), a wave a strip
@@ -262,6 +266,130 @@ __global__ __launch_bounds__(kCgBlock) void cg_start_kernel(const T* __restrict_
         mid = dn[k];
         emid = en[k];
         gmid = gn[k];
+      }
+    }
+  }
+
+  const Total t = grid_reduce(acc, static_cast<unsigned long long>(__double_as_longlong(from_bits(m))), partials, counter);
+  if (!t.last || threadIdx.x != 0) return;
+  const int max_iters = sc->max_iters;
+  sc->rr = t.sum;
+  sc->linf = t.linf;
+  if constexpr (kPcg) sc->rz = 0.0;
+  sc->pq = 0.0;
+  sc->alpha = 0.0;
+  sc->beta = 0.0;
+  sc->iteration = 0;
+  sc->status = cg_within(sc->norm, t.sum, t.linf, sc->tol) ? kCgConverged : (max_iters <= 0 ? kCgMaxIters : kCgRunning);
+}
+
+// ------------------------------------------------------------- cg_heat_start
+// The start of an implicit heat step (mxs/kernels/heat.hpp): cg_start_kernel
+// with the right-hand side made in the same pass. Per core cell, with S the
+// neighbour sum as cg_start forms it (ghosts included),
+//   g = fma(b, S, a c) (+ s q with SRC: the product rounded, then the sum)
+//   r = (fma(c1, S, 0 c) + g) - c
+// so r, rr and linf are those of cg_start_kernel on (u, the stored g) with
+// c0 = 0: same grid, same partials, same finish. Writes the cores of g, r (and
+// p); reads u as cg_start does and, with SRC, the core of q.
+template <typename T, typename S, bool NEU, bool SRC>
+__global__ __launch_bounds__(kCgBlock) void cg_heat_start_kernel(const T* __restrict__ u, const T* __restrict__ q,
+                                                                 T* __restrict__ g, T* __restrict__ r,
+                                                                 T* __restrict__ p, index_t pitch, index_t core_off,
+                                                                 index_t W, index_t H, unsigned gx, index_t band_rows,
+                                                                 T c1, T ha, T hb, T hs, int vec_ok, int mirror, S* sc,
+                                                                 double* partials, unsigned* counter) {
+  constexpr bool kPcg = std::is_same<S, PcgScalars>::value;
+  constexpr int N = CgVec<T>::N;
+  constexpr int kQ = SRC ? kCh : 1;  // no source: nothing of q is held or read
+  using V = typename CgVec<T>::type;
+  using U = decltype(abs_bits(T(0)));
+  const Strip<T> L(pitch, W, H, gx, band_rows, vec_ok);
+  const T* uc = u + core_off;
+  const T* qc = q + core_off;
+  T* gc = g + core_off;
+  T* rc = r + core_off;
+  T* pc = p + core_off;
+  const int nvalid = L.nvalid;
+
+  // Row y of u and its edge columns: cg_start_kernel's.
+  auto ldu = [&](index_t y) -> V {
+    const bool core_row = y >= 0 && y < H;
+    return L.ld(uc, y, nvalid == 0 ? 0 : (nvalid < N && core_row ? nvalid + 1 : nvalid));
+  };
+  auto lde = [&](index_t y) -> Edge<T> {  // core rows only
+    Edge<T> e{T(0), T(0)};
+    const T* a = uc + y * pitch + L.x;
+    if (L.left_load) e.l = a[-1];
+    if (L.right_load) e.r = a[N];
+    return e;
+  };
+
+  U m = 0;
+  double acc = 0.0;
+  if (L.any) {
+    V up = ldu(L.y0 - 1), mid = ldu(L.y0);
+    Edge<T> emid = lde(L.y0);
+    V qmid = V(T(0));
+    if constexpr (SRC) qmid = L.ld(qc, L.y0, nvalid);
+#pragma unroll 1
+    for (index_t y = L.y0; y < L.y1; y += kCh) {
+      V dn[kCh], qn[kQ];
+      Edge<T> en[kCh];
+#pragma unroll
+      for (int k = 0; k < kCh; ++k) {  // rows y + 1 .. y + kCh: row y1 <= H at most
+        const index_t yn = y + k + 1;
+        dn[k] = V(T(0));
+        en[k] = Edge<T>{T(0), T(0)};
+        if constexpr (SRC) qn[k] = V(T(0));
+        if (yn <= L.y1) dn[k] = ldu(yn);
+        if (yn < L.y1) {
+          en[k] = lde(yn);
+          if constexpr (SRC) qn[k] = L.ld(qc, yn, nvalid);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < kCh; ++k) {
+        if (y + k < L.y1) {
+          T left = lane_shift<kDppWaveShr1>(mid[N - 1]);  // lane i - 1's last element
+          T right = lane_shift<kDppWaveShl1>(mid[0]);      // lane i + 1's first
+          left = L.lane == 0 ? emid.l : left;
+          right = L.right_load ? emid.r : right;
+          V out, gout;
+#pragma unroll
+          for (int i = 0; i < N; ++i) {
+            const T w = i == 0 ? left : mid[i > 0 ? i - 1 : 0];
+            const T ea = i == N - 1 ? right : mid[i < N - 1 ? i + 1 : 0];
+            const T c = mid[i];
+            T sum;
+            if constexpr (NEU) {  // a mirror ghost is edge + ring (the ring holds d), one addition
+              const T nn = (mirror & kMirrorTop) && y + k == 0 ? c + up[i] : up[i];
+              const T ss = (mirror & kMirrorBottom) && y + k == H - 1 ? c + dn[k][i] : dn[k][i];
+              const T ww = (mirror & kMirrorLeft) && L.x + i == 0 ? c + w : w;
+              const T ee = (mirror & kMirrorRight) && L.x + i == W - 1 ? c + ea : ea;
+              sum = (nn + ss) + (ww + ee);
+            } else {
+              sum = (up[i] + dn[k][i]) + (w + ea);
+            }
+            T gv = fma_t<T>(hb, sum, ha * c);
+            if constexpr (SRC) gv = gv + hs * qmid[i];
+            T res = fma_t<T>(c1, sum, T(0) * c);
+            res = res + gv;
+            res = res - c;
+            res = i < nvalid ? res : T(0);  // a select: whatever sits past the core never enters
+            gout[i] = gv;
+            out[i] = res;
+            m = umax<U>(m, abs_bits(res));
+            acc = __builtin_fma(double(res), double(res), acc);
+          }
+          L.st(gc, y + k, gout);
+          L.st(rc, y + k, out);
+          if constexpr (!kPcg) L.st(pc, y + k, out);
+        }
+        up = mid;
+        mid = dn[k];
+        emid = en[k];
+        if constexpr (SRC) qmid = qn[k];
       }
     }
   }
@@ -548,6 +676,33 @@ void launch_start(const char* who, const T* u, const T* g, T* r, T* p, const Til
   MXS_HIP_CHECK_LAUNCH();
 }
 
+// The start of an implicit heat step: launch_start with g an output and the
+// optional source tile q (nullptr: the no-source kernel, q is never read).
+template <typename T, typename S>
+void launch_heat_start(const char* who, const T* u, const T* q, T* g, T* r, T* p, const TileGeom& geom,
+                       const HeatCoeffs& hc, S* scalars, double* partials, unsigned* counter, hipStream_t s,
+                       GhostSides sides) {
+  constexpr bool kPcg = std::is_same<S, PcgScalars>::value;
+  const CgGrid cg = kPcg ? check<T>(who, geom, {u, g, r}, scalars, partials, counter)
+                         : check<T>(who, geom, {u, g, r, p}, scalars, partials, counter);
+  MXS_CHECK(q == nullptr || reinterpret_cast<std::uintptr_t>(q) % sizeof(T) == 0, who << ": q must be element-aligned");
+  if (kPcg) MXS_CHECK(p == nullptr && u != r && g != r && u != g, who << ": u, g and r must be three tiles");
+  else MXS_CHECK(u != r && u != p && g != r && g != p && r != p && u != g, who << ": u, g, r and p must be four tiles (r != p)");
+  MXS_CHECK(q == nullptr || (q != g && q != r && q != p), who << ": the source q must not be one of the written tiles g, r, p");
+  constexpr int N = CgVec<T>::N;
+  const int vec_ok = geom.pitch % N == 0 && aligned16(u, geom) && aligned16(g, geom) && aligned16(r, geom) &&
+                     (kPcg || aligned16(p, geom)) && (q == nullptr || aligned16(q, geom));
+  const int mirror = mirror_mask(who, sides);
+  auto* kernel = q ? (mirror ? cg_heat_start_kernel<T, S, true, true> : cg_heat_start_kernel<T, S, false, true>)
+                   : (mirror ? cg_heat_start_kernel<T, S, true, false> : cg_heat_start_kernel<T, S, false, false>);
+  kernel<<<unsigned(index_t(cg.gx) * cg.bands), kCgBlock, 0, s>>>(u, q, g, r, p, geom.pitch, geom.core_offset(),
+                                                                  geom.width, geom.height, cg.gx, cg.band_rows, T(hc.c1),
+                                                                  T(hc.a), T(hc.b), T(hc.s), vec_ok, mirror, scalars,
+                                                                  partials, counter);
+  g_last_cg = who;
+  MXS_HIP_CHECK_LAUNCH();
+}
+
 // r: the residual, or with PcgScalars z = M r.
 template <typename T, typename S>
 void launch_apply(const char* who, const T* r, const T* p_old, T* p_new, T* q, const TileGeom& geom, Stencil5Coeffs c,
@@ -631,7 +786,30 @@ void pcg_update(T* u, T* r, const T* p, const T* q, const TileGeom& geom, PcgSca
   launch_update<T>("pcg_update", u, r, p, q, geom, scalars, partials, counter, s);
 }
 
-#define MXS_CG_INSTANTIATE(T)                                                                                       \
+// ------------------------------------------------------ implicit heat steps
+template <typename T>
+void cg_heat_start(const T* u, const T* q, T* g, T* r, T* p, const TileGeom& geom, const HeatCoeffs& hc,
+                   CgScalars* scalars, double* partials, unsigned* counter, hipStream_t s, GhostSides sides) {
+  launch_heat_start<T>("cg_heat_start", u, q, g, r, p, geom, hc, scalars, partials, counter, s, sides);
+}
+
+template <typename T>
+void pcg_heat_start(const T* u, const T* q, T* g, T* r, const TileGeom& geom, const HeatCoeffs& hc,
+                    PcgScalars* scalars, double* partials, unsigned* counter, hipStream_t s, GhostSides sides) {
+  launch_heat_start<T>("pcg_heat_start", u, q, g, r, static_cast<T*>(nullptr), geom, hc, scalars, partials, counter, s,
+                       sides);
+}
+
+#define MXS_HEAT_INSTANTIATE(T)                                                                                       \
+  template void cg_heat_start<T>(const T*, const T*, T*, T*, T*, const TileGeom&, const HeatCoeffs&, CgScalars*,      \
+                                 double*, unsigned*, hipStream_t, GhostSides);                                        \
+  template void pcg_heat_start<T>(const T*, const T*, T*, T*, const TileGeom&, const HeatCoeffs&, PcgScalars*,        \
+                                  double*, unsigned*, hipStream_t, GhostSides);
+MXS_HEAT_INSTANTIATE(float)
+MXS_HEAT_INSTANTIATE(double)
+#undef MXS_HEAT_INSTANTIATE
+
+#define MXS_CG_INSTANTIATE(T)                                                                                    \
   template void cg_start<T>(const T*, const T*, T*, T*, const TileGeom&, Stencil5Coeffs, CgScalars*, double*,       \
                             unsigned*, hipStream_t, GhostSides);                                                    \
   template void cg_apply<T>(const T*, const T*, T*, T*, const TileGeom&, Stencil5Coeffs, CgScalars*, double*,       \

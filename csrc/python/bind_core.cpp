@@ -14,6 +14,7 @@
 #include "mxs/kernels/cg.hpp"
 #include "mxs/kernels/chunk_schedule.hpp"
 #include "mxs/kernels/fixed_edge_split.hpp"
+#include "mxs/kernels/heat.hpp"
 #include "mxs/kernels/multigrid.hpp"
 #include "mxs/kernels/pcg.hpp"
 #include "mxs/kernels/relaxation.hpp"
@@ -341,6 +342,22 @@ PYBIND11_MODULE(_mxs_core, m) {
   m.def("cg_check_operator", &kernels::cg_check_operator, py::arg("c_center"), py::arg("c_neighbor"),
         "raises ValueError unless c_neighbor > 0 and c_center + 4 c_neighbor <= 1 + 1e-12 (then (1 - c_center) v - "
         "c_neighbor (n + s + w + e) is symmetric positive definite)");
+  // Implicit heat steps (kernels/heat.hpp).
+  m.def(
+      "heat_coefficients",
+      [](double lam, double theta) {
+        const kernels::HeatCoeffs h = kernels::heat_coefficients(lam, theta);
+        py::dict d;
+        d["c1"] = h.c1;
+        d["a"] = h.a;
+        d["b"] = h.b;
+        d["s"] = h.s;
+        return d;
+      },
+      py::arg("lam"), py::arg("theta") = 1.0,
+      "the theta-scheme step as the fixed-edge problem u' = A u' + g: {c1, a, b, s} with D = 1 + 4 theta lam, c1 = theta "
+      "lam / D (c_center = 0), g = a u + b (n + s + w + e) + s q, s = 1 / D; raises ValueError for lam <= 0, non-finite "
+      "input or theta outside [0.5, 1]");
   // Preconditioned CG (kernels/pcg.hpp): the any-size level plan and the coarse solve plan.
   auto pcg_level_dict = [](const kernels::PcgLevel& l) {
     py::dict d;

@@ -232,6 +232,31 @@ void def_cg_methods(py::class_<Handle>& c, int max_iters, int check_every, const
        },
        py::arg("tol"), py::arg("max_iters") = max_iters, py::arg("norm") = "l2", py::arg("check_every") = check_every,
        solve_doc)
+      .def(
+          "step",
+          [](Handle& h, double lam, double theta, double tol, int max_iters, const std::string& norm, int check_every) {
+            const kernels::HeatCoeffs hc = kernels::heat_coefficients(lam, theta);
+            CgSolve r;
+            {
+              py::gil_scoped_release nogil;
+              r = h.visit([&](auto& s) { return s.step(hc, tol, max_iters, norm, check_every); });
+            }
+            return cg_solve_dict(r);
+          },
+          py::arg("lam"), py::arg("theta"), py::arg("tol"), py::arg("max_iters") = max_iters, py::arg("norm") = "l2",
+          py::arg("check_every") = check_every,
+          "one implicit heat step (heat_coefficients(lam, theta)): solve() whose first start launch is the fused heat "
+          "start, which makes the step's right-hand side from the field and the step source and stores it as g; "
+          "raises unless the solver's weights are (0, c1)")
+      .def(
+          "set_step_source",
+          [](Handle& h, std::uintptr_t tile) {
+            h.visit([&](auto& s) {
+              using T = typename std::decay_t<decltype(s)>::value_type;
+              s.set_step_source(ptr<T>(tile));
+            });
+          },
+          py::arg("tile") = 0, "a device tile of geom() whose core holds q = dt f of the steps to come, or 0 (none)")
       .def("scalars", [](Handle& h) { return h.visit([](auto& s) { return scalars_dict(s.scalars()); }); },
            "the device scalar block as a dict (a synchronising read)");
 }
@@ -1235,6 +1260,24 @@ PYBIND11_MODULE(_mxs_hip, m) {
       "r = p = (fma(c1, (n + s) + (w + e), c0 v) + g) - v over the core; last workgroup: rr, linf, beta = 0, "
       "iteration = 0, status");
   m.def(
+      "cg_heat_start",
+      [](std::uintptr_t u, std::uintptr_t q, std::uintptr_t g, std::uintptr_t r, std::uintptr_t p, const TileGeom& geom,
+         double lam, double theta, std::uintptr_t scalars, std::uintptr_t partials, std::uintptr_t counter,
+         const std::string& dt, std::uintptr_t s, const std::array<int, 4>& sides) {
+        const kernels::HeatCoeffs hc = kernels::heat_coefficients(lam, theta);
+        if (parse_dtype(dt) == DType::F32)
+          kernels::cg_heat_start<float>(ptr<float>(u), ptr<float>(q), ptr<float>(g), ptr<float>(r), ptr<float>(p), geom, hc,
+                                        ptr<kernels::CgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s), ghost_sides(sides));
+        else
+          kernels::cg_heat_start<double>(ptr<double>(u), ptr<double>(q), ptr<double>(g), ptr<double>(r), ptr<double>(p), geom, hc,
+                                         ptr<kernels::CgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s), ghost_sides(sides));
+      },
+      py::arg("u"), py::arg("q"), py::arg("g"), py::arg("r"), py::arg("p"), py::arg("geom"), py::arg("lam"),
+      py::arg("theta"), py::arg("scalars"), py::arg("partials"), py::arg("counter"), py::arg("dtype") = "f64",
+      py::arg("stream") = 0, py::arg("sides") = kNoSides,
+      "the start of an implicit heat step: g = fma(b, S, a v) (+ s q; q = 0: no source), r = p = (fma(c1, S, 0 v) + g) "
+      "- v over the core with S = (n + s) + (w + e); last workgroup: as cg_start");
+  m.def(
       "cg_apply",
       [](std::uintptr_t r, std::uintptr_t p_old, std::uintptr_t p_new, std::uintptr_t q, const TileGeom& geom, double c0,
          double c1, std::uintptr_t scalars, std::uintptr_t partials, std::uintptr_t counter, const std::string& dt,
@@ -1311,6 +1354,23 @@ PYBIND11_MODULE(_mxs_hip, m) {
       py::arg("scalars"), py::arg("partials"), py::arg("counter"), py::arg("dtype") = "f64", py::arg("stream") = 0, py::arg("sides") = kNoSides,
       "r = (fma(c1, (n + s) + (w + e), c0 v) + g) - v over the core; last workgroup: rr, linf, rz = beta = 0, "
       "iteration = 0, status");
+  m.def(
+      "pcg_heat_start",
+      [](std::uintptr_t u, std::uintptr_t q, std::uintptr_t g, std::uintptr_t r, const TileGeom& geom, double lam,
+         double theta, std::uintptr_t scalars, std::uintptr_t partials, std::uintptr_t counter, const std::string& dt,
+         std::uintptr_t s, const std::array<int, 4>& sides) {
+        const kernels::HeatCoeffs hc = kernels::heat_coefficients(lam, theta);
+        if (parse_dtype(dt) == DType::F32)
+          kernels::pcg_heat_start<float>(ptr<float>(u), ptr<float>(q), ptr<float>(g), ptr<float>(r), geom, hc,
+                                         ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s), ghost_sides(sides));
+        else
+          kernels::pcg_heat_start<double>(ptr<double>(u), ptr<double>(q), ptr<double>(g), ptr<double>(r), geom, hc,
+                                          ptr<kernels::PcgScalars>(scalars), ptr<double>(partials), ptr<unsigned>(counter), strm(s), ghost_sides(sides));
+      },
+      py::arg("u"), py::arg("q"), py::arg("g"), py::arg("r"), py::arg("geom"), py::arg("lam"), py::arg("theta"),
+      py::arg("scalars"), py::arg("partials"), py::arg("counter"), py::arg("dtype") = "f64", py::arg("stream") = 0,
+      py::arg("sides") = kNoSides,
+      "cg_heat_start on a PcgScalars block: g and r over the core, no first direction; last workgroup: as pcg_start");
   m.def(
       "pcg_apply",
       [](std::uintptr_t z, std::uintptr_t p_old, std::uintptr_t p_new, std::uintptr_t q, const TileGeom& geom, double c0,

@@ -76,7 +76,7 @@ S CgSolverBase<T, S>::read_scalars() {
 }
 
 template <typename T, typename S>
-S CgSolverBase<T, S>::start(double tol, int max_iters, int norm) {
+S CgSolverBase<T, S>::start(double tol, int max_iters, int norm, const kernels::HeatCoeffs* heat) {
   hipStream_t s = stream_.get();
   S& up = scalars_host_.get()[0];
   up = S{};
@@ -85,7 +85,8 @@ S CgSolverBase<T, S>::start(double tol, int max_iters, int norm) {
   up.norm = norm;
   MXS_HIP_CHECK(hipMemcpyAsync(scalars_.get(), &up, sizeof(up), hipMemcpyHostToDevice, s));
   MXS_HIP_CHECK(hipMemsetAsync(counter_.get(), 0, sizeof(unsigned), s));
-  launch_start(false);
+  if (heat) launch_heat_start(*heat, step_source_ ? step_q_.get() : nullptr);
+  else launch_start(false);
   return read_scalars();
 }
 
@@ -97,7 +98,36 @@ bool CgSolverBase<T, S>::capture(int iters) {
 }
 
 template <typename T, typename S>
+void CgSolverBase<T, S>::set_step_source(const T* tile) {
+  step_source_ = tile != nullptr;
+  if (!tile) return;
+  if (step_q_.size() == 0) step_q_.reset(geom_.alloc_elems());
+  MXS_HIP_CHECK(hipMemcpyAsync(step_q_.get(), tile, step_q_.bytes(), hipMemcpyDeviceToDevice, stream_.get()));
+  stream_.sync();
+}
+
+template <typename T, typename S>
 CgSolve CgSolverBase<T, S>::solve(double tol, int max_iters, const std::string& norm, int check_every) {
+  return drive(nullptr, tol, max_iters, norm, check_every);
+}
+
+template <typename T, typename S>
+CgSolve CgSolverBase<T, S>::step(const kernels::HeatCoeffs& hc, double tol, int max_iters, const std::string& norm,
+                                 int check_every) {
+  if (c_center_ != 0.0 || c_neighbor_ != hc.c1) {
+    std::ostringstream os;
+    os.precision(17);
+    os << who_ << ": step() needs a solver built with the step's own weights (c_center, c_neighbor) = (0, " << hc.c1
+       << "); this one has (" << c_center_ << ", " << c_neighbor_ << ")";
+    throw std::invalid_argument(os.str());
+  }
+  return drive(&hc, tol, max_iters, norm, check_every);
+}
+
+// heat: the first run starts with the fused heat start; a restart takes the ordinary one on the stored g.
+template <typename T, typename S>
+CgSolve CgSolverBase<T, S>::drive(const kernels::HeatCoeffs* heat, double tol, int max_iters, const std::string& norm,
+                                  int check_every) {
   int block = check_every;
   if (graph_on_) block += block & 1;  // even: the p ping-pong closes inside the graph
   int parity = 0;                     // of the eager path: the p buffer the next block reads
@@ -108,7 +138,9 @@ CgSolve CgSolverBase<T, S>::solve(double tol, int max_iters, const std::string& 
         // Here, not above: cg_drive has checked the arguments by now.
         if (graph_on_ && graph_iters_ != block) capture(block);
         parity = 0;
-        return progress(start(run_tol, remaining, norm_id));
+        const kernels::HeatCoeffs* first = heat;
+        heat = nullptr;
+        return progress(start(run_tol, remaining, norm_id, first));
       },
       [&] {
         if (graph_.valid()) {
@@ -147,6 +179,13 @@ void CgSolver<T>::launch_start(bool into_scratch) {
                        this->p_[into_scratch ? 1 : 0].get(), this->geom_, this->coeffs(),
                        (into_scratch ? this->residual_scalars_ : this->scalars_).get(), this->partials_.get(),
                        this->counter_.get(), this->stream_.get(), this->sides_);
+}
+
+template <typename T>
+void CgSolver<T>::launch_heat_start(const kernels::HeatCoeffs& hc, const T* q) {
+  kernels::cg_heat_start<T>(this->u_.get(), q, this->g_.get(), this->r_.get(), this->p_[0].get(), this->geom_, hc,
+                            this->scalars_.get(), this->partials_.get(), this->counter_.get(), this->stream_.get(),
+                            this->sides_);
 }
 
 template <typename T>

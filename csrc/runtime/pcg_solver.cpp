@@ -47,6 +47,14 @@ void PcgSolver<T>::launch_start(bool into_scratch) {
                         this->partials_.get(), this->counter_.get(), s, this->sides_);
 }
 
+template <typename T>
+void PcgSolver<T>::launch_heat_start(const kernels::HeatCoeffs& hc, const T* q) {
+  hipStream_t s = this->stream_.get();
+  MXS_HIP_CHECK(hipMemsetAsync(this->p_[0].get(), 0, this->p_[0].bytes(), s));  // as launch_start
+  kernels::pcg_heat_start<T>(this->u_.get(), q, this->g_.get(), this->r_.get(), this->geom_, hc, this->scalars_.get(),
+                             this->partials_.get(), this->counter_.get(), s, this->sides_);
+}
+
 // z = M r into lv_[0].u[0]: level k's source is r (k == 0) or its own g, its
 // iterate starts at 0 (mgp_smooth's start from zero), the pre-smooth writes
 // u[1], the coarse correction is added there and the post-smooth writes u[0]. The last launch

@@ -7,6 +7,8 @@ from .dot import DotWorkspace, dot  # noqa: F401
 from .exact import (box_exact_reference, jacobi_sum_block_reference, stencil5_exact_block_reference,  # noqa: F401
                     stencil5_exact_periodic_reference, stencil5_exact_reference)
 from .fill import fill, fill_random, fill_region, random_values  # noqa: F401
+from .heat import (cg_heat_start, heat_coefficients, heat_rhs_reference, heat_start_reference,  # noqa: F401
+                   heat_step_reference, pcg_heat_start)
 from .multigrid import (mg_coarse_plan, mg_coarse_solve, mg_coarse_solve_reference, mg_plan_levels,  # noqa: F401
                         mg_prolong_add, mg_prolong_add_reference, mg_prolong_reference, mg_residual_reference,
                         mg_residual_restrict, mg_residual_restrict_reference, mg_restrict_reference, mg_smooth,
